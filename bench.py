@@ -123,6 +123,46 @@ def logloss(p, y):
     return float(np.mean(-np.where(y == 1, np.log(p), np.log(1 - p))))
 
 
+DUMP_BLOCKS, DUMP_BLOCK = 256, 4096  # --dump-outputs: per table, 256 blocks of 4096 consecutive floats (4 MiB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(re, capi, fbt, records, rec_off, sync, stream, out_dir, seed):
+    """--dump-outputs, as float32 .npy files.  The timed steps run concurrently (hogwild: unsynchronised read-modify-write of rows that many
+    examples hold), so the model they leave and every prediction made from it depend on timing and differ from run to run on the same inputs.
+    What is written instead is a function of the inputs and the build alone, so that two builds can be compared output for output: the last timed
+    step's records through the step's own entry (learn_batch, or learn_batch_sync for synchronous steps) on `re`, a FRESH model of the same
+    configuration, in the library's in-order mode (FWGPU_MODE_SEQUENTIAL: one workgroup walking the batch in example order; launches that are
+    concurrent-only -- store policies 3 / 4, the small-example shape, the head as a phase -- do not run there) -> inorder_predictions and the
+    tables it updated (whole, or DUMP_BLOCKS blocks at offsets drawn from a fixed seed where a table is larger); then a predict-only CONCURRENT
+    launch of the timed steps' shape over the same records on that model -> concurrent_predictions (no writes: nothing races)."""
+    b = re.record_batch(fbt, records, rec_off)
+    if sync:
+        re.learn_batch_sync(b, re.split_buffers(b.n, 1024), capi.MODE_SEQUENTIAL, stream)
+    else:
+        re.learn_batch(b, capi.MODE_SEQUENTIAL, True, stream)
+    arrays = {"inorder_predictions": b.predictions(stream)}
+    tables = {"lr_table": capi.TABLE_LR, "ffm_weights": capi.TABLE_FFM_W, "ffm_accumulators": capi.TABLE_FFM_ACC,
+              "nn_weights": capi.TABLE_NN_W, "nn_accumulators": capi.TABLE_NN_ACC}
+    for name, which in tables.items():
+        n = re.table_len(which)
+        if n == 0:  # (no deep head)
+            continue
+        if n <= DUMP_BLOCKS * DUMP_BLOCK:
+            arrays["inorder_" + name] = re.table_read(which)
+        else:
+            rng = np.random.default_rng([seed, which])
+            starts = np.sort(rng.choice(n // DUMP_BLOCK, DUMP_BLOCKS, replace=False)) * DUMP_BLOCK
+            arrays["inorder_" + name + "_sample"] = np.concatenate([re.table_read(which, int(s), DUMP_BLOCK) for s in starts])
+    re.learn_batch(b, capi.MODE_HOGWILD, False, stream)
+    arrays["concurrent_predictions"] = b.predictions(stream)
+    b.close()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+
+
 def oracle_reference_curves(args, world, holdout=None):
     """Hold-out log-loss of the reference algorithm on this very stream and hold-out tail after N examples: numbers produced by
     scripts/make_bench_oracle_curve.py from the CPU oracle and committed as data (tests/golden/bench_oracle_curve_*.json) -- the reference's single
@@ -688,7 +728,12 @@ def main():
     ap.add_argument("--store-policy", dest="store_policy", type=int, default=None, choices=[0, 1, 2, 3, 4], help="A/B: FFM row store policy (kernels.hip top); default = the build's")
     ap.add_argument("--launch-timeout", dest="launch_timeout", type=float, default=900.0,
                     help="self-launched N>1 run (no WORLD_SIZE in the environment): seconds after which the parent ends its ranks and exits non-zero")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 replays the last step's records on a fresh model in the in-order mode and writes its predictions, "
+                         "a seeded sample of its tables and a concurrent predict-only pass as DIR/<name>.npy (float32), the same every run")
     args = ap.parse_args()
+    if args.dump_outputs and args.long:
+        ap.error("--dump-outputs is not supported with --long")
     apply_family(args, args.family)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` as the driver types it for N = 1, with nothing else set: be the launcher
@@ -715,6 +760,8 @@ def main():
         raise SystemExit("bench.py needs a GPU (there is no CPU path)")
     torch.cuda.set_device(local_rank)
     use_dist = world > 1 or args.force_dist
+    if args.dump_outputs and use_dist and args.dp_mode != "replica":
+        raise SystemExit(f"--dump-outputs: the steps of --dp-mode {args.dp_mode} are collectives across the ranks, which one rank's model cannot replay")
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -725,17 +772,22 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
     mi = build_model_instance(fw, args, local_rank)
-    re = fw.Regressor(mi)
-    if args.whole_lines is not None:
-        re.set_whole_line_updates(args.whole_lines)
-    if os.environ.get("FWGPU_BENCH_NO_CHAIN"):
-        capi.check(capi.lib().fwgpu_debug_set_option(re.h, 3, 1))
-    if args.threads or args.wgs:
-        re.set_launch(args.threads, args.wgs)
-    if args.max_in_flight:
-        re.set_max_in_flight(args.max_in_flight)
-    if args.store_policy is not None:
-        re.set_store_policy(args.store_policy)
+
+    def new_regressor():
+        r = fw.Regressor(mi)
+        if args.whole_lines is not None:
+            r.set_whole_line_updates(args.whole_lines)
+        if os.environ.get("FWGPU_BENCH_NO_CHAIN"):
+            capi.check(capi.lib().fwgpu_debug_set_option(r.h, 3, 1))
+        if args.threads or args.wgs:
+            r.set_launch(args.threads, args.wgs)
+        if args.max_in_flight:
+            r.set_max_in_flight(args.max_in_flight)
+        if args.store_policy is not None:
+            r.set_store_policy(args.store_policy)
+        return r
+
+    re = new_regressor()
     fbt = fw.FeatureBufferTranslator(mi)
 
     sync_steps = args.sync or (args.nn_layers > 0 and args.head == "minibatch")
@@ -755,6 +807,8 @@ def main():
         # raw records in HBM; FeatureBufferTranslator::translate (a2) runs inside the kernel's stage phase
         batches.append(re.record_batch(fbt, sub, off[lo:hi + 1] - off[lo]))
         words.append(len(sub))
+        if s == W + K - 1 and args.dump_outputs:
+            last_records = (sub.copy(), off[lo:hi + 1] - off[lo])
         blabels.append(sub[(off[lo:hi] - off[lo]).astype(np.int64) + 1].astype(np.float32))
     hrecs, hoff = gen_records(fw, args, 1_000_000_000, args.holdout)  # same hold-out tail on every rank
     hbatch = re.record_batch(fbt, hrecs, hoff)
@@ -922,6 +976,10 @@ def main():
                                "what": "last timed step of rank 0: occurrences (entries of the micro-batch) vs deduplicated bucket rows put on the wire"}
         else:
             dist_rank.gather_tables()  # every rank gets the whole model back for the hold-out pass
+    if args.dump_outputs and rank == 0:
+        rd = new_regressor()
+        dump_outputs(rd, capi, fbt, *last_records, sync_steps, sptr, args.dump_outputs, args.seed)
+        rd.close()
     avg_kernel_ms = float(np.mean(kernel_ms))
     alg_bytes = float(np.mean([algorithmic_bytes(args, batches[W + i], words[W + i]) for i in range(K)]))
 

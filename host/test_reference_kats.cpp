@@ -385,12 +385,15 @@ static void test_vowpal() {
     ASSERT_TRUE(r2.next_vowpal_with_cache("|BB b ", "|AA:3 a:2.0 \n") == full);
 }
 
+// where test_cache_model_file_and_predictor writes its files: argv[1] (the caller's scratch directory), else $TMPDIR or /tmp
+static std::string g_work_dir;
+
 // cache.rs + persistence.rs + lib.rs in one chain (persistence.rs:206-643 style: what is saved predicts the same when loaded)
 static void test_cache_model_file_and_predictor() {
     VwNamespaceMap vw("A,animal\nB,food\n");
     VowpalParser pa(vw);
-    const std::string dir = "/tmp/fw_host_test";
-    std::system(("rm -rf " + dir + " && mkdir -p " + dir).c_str());
+    const std::string dir = g_work_dir + "/fw_host_test";
+    std::system(("rm -rf '" + dir + "' && mkdir -p '" + dir + "'").c_str());
     const std::string input = dir + "/train.vw";
     std::vector<std::vector<uint32_t>> recs;
     {
@@ -449,7 +452,9 @@ static void test_cache_model_file_and_predictor() {
     ASSERT_TRUE(fresh.write_weights_to_buf() == re.write_weights_to_buf());
 }
 
-int main() {
+int main(int argc, char **argv) {
+    const char *tmp = std::getenv("TMPDIR");
+    g_work_dir = argc > 1 ? argv[1] : (tmp && *tmp ? tmp : "/tmp");
     struct T {
         const char *name;
         void (*fn)();

@@ -1,6 +1,6 @@
 """bench.py as its own launcher (`python3 bench.py --gpus N` with no WORLD_SIZE): what can be checked without a GPU -- the parent imports neither
 torch nor the library, gives every rank the torchrun environment, relays rank 0's stdout only, and comes back non-zero when a rank fails
-(here every rank does: there is no GPU and no CPU path)."""
+(here every rank does: the ranks are shown no GPU, HIP_VISIBLE_DEVICES=-1, and there is no CPU path -- on a machine with GPUs as on one without)."""
 import os
 import subprocess
 import sys
@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_self_launch_without_gpu_fails_loudly_and_quickly():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")  # (no device visible to the ranks, whatever the machine has)
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0

@@ -952,13 +952,12 @@ def test_table_torch_view_is_zero_copy():
 
 
 # ------------------------------------------------------------------ the C++ host mirror, reference-style tests
-def test_cpp_host_mirror_reference_tests():
+def test_cpp_host_mirror_reference_tests(tmp_path):
     import subprocess
 
     exe = os.path.join(ROOT, "host", "test_reference_kats")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "host")], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    subprocess.run(["make", "-C", os.path.join(ROOT, "host")], check=True)  # (a binary older than its sources would not take the work directory)
+    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all 16 tests passed" in r.stdout
 

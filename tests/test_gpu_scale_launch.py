@@ -1,9 +1,11 @@
 """The driver's multi-GPU launch of bench.py (scripts/scale_run.sh = `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`)
-with N = 8 PROCESSES on the one GPU of this box: torch.distributed over gloo as the side channel, the library's own communicator over the
+with N PROCESSES on one GPU: torch.distributed over gloo as the side channel, the library's own communicator over the
 shared-memory stand-in of tests/fake_rccl.  What it pins before a real node runs it: the launcher starts before any GPU call (the script
-execs the launcher from bash), eight ranks come up at once on one device (eight regressors' placement searches, eight communicators),
+execs the launcher from bash), N ranks come up at once on one device (N regressors' placement searches, N communicators),
 the timed replica exchange, the sparse and sharded legs and the peer-sharded mode with its IPC-mapped tables (incl. the LR-shard
-workaround for hipIpcOpenMemHandle) all complete, and the line reports the communicator's own rank count.  Functional, not a rate."""
+workaround for hipIpcOpenMemHandle) all complete, and the line reports the communicator's own rank count.  Functional, not a rate.
+N = RANKS = 4: every rank is a process with the GPU open, beside the test runner's own; four keeps the run within the few such processes at once
+that a GPU shared with other jobs admits."""
 import json
 import os
 import subprocess
@@ -12,6 +14,7 @@ import sys
 import pytest
 
 pytestmark = pytest.mark.gpu
+RANKS = 4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -26,9 +29,9 @@ def _launch(n, *flags, timeout=900):
     return json.loads(lines[-1])
 
 
-def test_eight_ranks_replica_mode_with_the_sparse_and_sharded_legs():
-    d = _launch(8)
-    assert d["n_gpus"] == 8 and d["rccl_ranks"] == 8, (d["n_gpus"], d.get("rccl_ranks"))
+def test_four_ranks_replica_mode_with_the_sparse_and_sharded_legs():
+    d = _launch(RANKS)
+    assert d["n_gpus"] == RANKS and d["rccl_ranks"] == RANKS, (d["n_gpus"], d.get("rccl_ranks"))
     assert d["value"] > 0 and 0.3 < d["final_logloss"] < 0.70
     assert "error" not in d.get("dp_modes", {}), d.get("dp_modes")
     assert d["dp_modes"]["sparse"]["value"] > 0 and d["dp_modes"]["sharded"]["value"] > 0
@@ -36,9 +39,9 @@ def test_eight_ranks_replica_mode_with_the_sparse_and_sharded_legs():
     assert lb["owner_apply"] < lb["peer"] < lb["sparse_upper_bound"]
 
 
-def test_eight_ranks_peer_sharded_mode():
-    d = _launch(8, "--dp-mode", "peer", "--no-other-modes")
-    assert d["n_gpus"] == 8 and d["rccl_ranks"] == 8
+def test_four_ranks_peer_sharded_mode():
+    d = _launch(RANKS, "--dp-mode", "peer", "--no-other-modes")
+    assert d["n_gpus"] == RANKS and d["rccl_ranks"] == RANKS
     assert d["value"] > 0 and 0.3 < d["final_logloss"] < 0.70
 
 
@@ -57,14 +60,14 @@ def _self_launch(n, *flags, timeout=900, env_extra=None):
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 
 
-def test_bench_launches_its_own_eight_ranks_when_no_launcher_set_world_size():
-    p = _self_launch(8)
+def test_bench_launches_its_own_four_ranks_when_no_launcher_set_world_size():
+    p = _self_launch(RANKS)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]  # rank 0's line, once
     d = json.loads(lines[-1])
     assert p.stdout.rstrip().splitlines()[-1] == lines[-1]  # and it is the last line of stdout
-    assert d["n_gpus"] == 8 and d["rccl_ranks"] == 8, (d["n_gpus"], d.get("rccl_ranks"))
+    assert d["n_gpus"] == RANKS and d["rccl_ranks"] == RANKS, (d["n_gpus"], d.get("rccl_ranks"))
     assert d["value"] > 0 and 0.3 < d["final_logloss"] < 0.70
     assert "error" not in d.get("dp_modes", {}), d.get("dp_modes")
 
