@@ -8,6 +8,10 @@ A "step" is one pass of the learn path over one micro-batch of synthetic records
 30 fields, k=8, 28-bit hashes, ~200 nnz/example, AdagradLUT) with the translated batch already resident in HBM.
 Rank 0 prints ONE JSON line (see the driver contract in the task description).
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line.  `--full` adds every side figure and
+check: the CPU baseline, the other configurations' legs, the host-fed rate, live traffic, the copy peak, the CPU oracle's curves and, N > 1,
+the other multi-GPU modes.
+
 N > 1: every rank owns a full replica and trains on its own shard of the stream (weak scaling); replicas are
 kept together by an RCCL all-reduce of the weight/accumulator deltas every --sync-every steps (DESIGN.md,
 "Multi-GPU").  The syncs that fall inside the timed steps are timed.
@@ -79,13 +83,34 @@ def _flip_mask(seed, first, n, frac):
     return (x >> np.uint64(11)).astype(np.float64) * (1.0 / (1 << 53)) < frac
 
 
-def gen_records(fw, args, first, n, threads=8):
-    """Synthetic stream [first, first+n) in chunks on a thread pool (ctypes releases the GIL)."""
+def synth_one_pass(args, first, n):
+    """fw.synth_records with one pass of the generator instead of two (sizing the stream, then writing it): fwgpu_synth_records writes straight
+    into room for n of the longest records the configuration can produce -- the 3-word header, one slot per namespace and at most 64 (hash,
+    value) pairs per namespace (translate.cpp) -- and the words it wrote are returned.  The same records and offsets."""
+    import ctypes as C
+
+    from fwumious_wabbit_amd import _capi as capi
+
+    cap = n * (3 + args.fields * (1 + 2 * 64))
+    records = np.empty(cap, dtype=np.uint32)  # (only the pages written become resident)
+    rec_off = np.zeros(n + 1, dtype=np.uint64)
+    nw = C.c_uint64(0)
+    cfg = capi.SynthConfig(args.fields, args.mean_extra, args.zipf, args.ids, args.p_weighted, args.seed)
+    capi.check(capi.lib().fwgpu_synth_records(C.byref(cfg), first, n, capi.ptr(records), cap, capi.ptr(rec_off), C.byref(nw)))
+    return records[: nw.value], rec_off
+
+
+GEN_THREADS = min(16, len(os.sched_getaffinity(0)))  # the host CPUs this process may use, at most 16
+
+
+def gen_records(fw, args, first, n, threads=GEN_THREADS):
+    """Synthetic stream [first, first+n) in chunks on a thread pool (ctypes releases the GIL); every example is a function of its number
+    alone, so the records do not depend on the number of threads."""
     chunk = 2048
     jobs = [(first + s, min(chunk, n - s)) for s in range(0, n, chunk)]
 
     def one(j):
-        return fw.synth_records(args.fields, args.mean_extra, args.zipf, args.ids, args.p_weighted, args.seed, j[0], j[1])
+        return synth_one_pass(args, j[0], j[1])
 
     with ThreadPoolExecutor(max_workers=threads) as ex:
         parts = list(ex.map(one, jobs))
@@ -353,10 +378,10 @@ def _child_leg(cmd, timeout=420, env=None):
 
 def config_e_leg(args):
     """BASELINE configs[4] next to the headline line: a short child run of this script with k = 16 and the 2 x 256 ReLU head (exact
-    per-example head, hogwild), so that the driver's default invocation measures it too.  A reported side figure, never `value`.
+    per-example head, hogwild), so that a --full run of the default shape measures it too.  A reported side figure, never `value`.
     `oracle_final_logloss`: the sequential CPU oracle on the same 229 376 examples and the same hold-out (tests/golden/bench_oracle_curve_confige_seq.json)."""
     cmd = [sys.executable, os.path.abspath(__file__), "--k", "16", "--nn-layers", "2", "--nn-width", "256", "--head", "exact", "--batch", "8192",
-           "--steps", "24", "--warmup", "4", "--holdout", "65536", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b",
+           "--steps", "24", "--warmup", "4", "--holdout", "65536", "--full", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b",
            "--fields", str(args.fields), "--bits", str(args.bits), "--ffm-bits", str(args.ffm_bits)]
     try:
         d = _child_leg(cmd)
@@ -371,7 +396,7 @@ def no_kept_rows_leg(args, steps, warmup):
     """The same stream and the same number of launches with NO rows kept from the gather (fwgpu_debug_set_option 13 = 0 / FWGPU_KEPT_ROWS=0: every row re-read by the update, no
     last-writer-wins over an example's lifetime): the concurrent mode whose hold-out curve on this stream IS the reference's (profiles/r06_kept_rows_long.txt) -- 14 % slower,
     and on the second stream family 0.004 above the reference where the shipped mode is on it.  A reported side figure, never `value`."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b",
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b",
            "--fields", str(args.fields), "--k", str(args.k), "--bits", str(args.bits), "--ffm-bits", str(args.ffm_bits), "--holdout", str(args.holdout)]
     try:
         d = _child_leg(cmd, env=dict(os.environ, FWGPU_KEPT_ROWS="0"))
@@ -388,7 +413,7 @@ def config_b_leg(args):
     reported against the HBM peak all the same, with the oracle's loss on the same 901 120 examples beside the GPU's."""
     cmd = [sys.executable, os.path.abspath(__file__), "--fields", "10", "--k", "4", "--bits", "22", "--ffm-bits", "22", "--mean-extra", "0", "--zipf", "1.1",
            "--ids", "100000", "--p-weighted", "0", "--seed", "20240611", "--lr", "0.1", "--power-t", "0.5", "--batch", "4096", "--steps", "200", "--warmup", "20",
-           "--holdout", "65536", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b"]
+           "--holdout", "65536", "--full", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b"]
     try:
         d = _child_leg(cmd)
         return {"value": d["value"], "unit": d["unit"], "final_logloss": d["final_logloss"], "oracle_final_logloss": d.get("oracle_final_logloss"),
@@ -713,9 +738,9 @@ def main():
                     help="seconds_to_logloss target (default: 0.985 x the loss of always predicting the hold-out's positive rate)")
     ap.add_argument("--no-cpu-baseline", dest="cpu", action="store_false")
     ap.add_argument("--no-config-e", dest="config_e", action="store_false",
-                    help="skip the short config-E leg (k = 16 + 2 x 256 ReLU head, a child run) that the default single-GPU line reports as `config_e`")
+                    help="skip the short config-E leg (k = 16 + 2 x 256 ReLU head, a child run) that the single-GPU --full line reports as `config_e`")
     ap.add_argument("--no-config-b", dest="config_b", action="store_false",
-                    help="skip the short config-B leg (10 fields, k = 4, 22-bit tables, micro-batch 4096: a child run) that the default single-GPU line reports as `config_b`")
+                    help="skip the short config-B leg (10 fields, k = 4, 22-bit tables, micro-batch 4096: a child run) that the single-GPU --full line reports as `config_b`")
     ap.add_argument("--cpu-examples", dest="cpu_examples", type=int, default=0)
     ap.add_argument("--lr", type=float, default=LR, help="learning rate of the LR and FFM blocks (default: run_one.sh's 0.025; config B: 0.1, SURVEY 8d)")
     ap.add_argument("--power-t", dest="power_t", type=float, default=POWER_T)
@@ -728,6 +753,11 @@ def main():
     ap.add_argument("--store-policy", dest="store_policy", type=int, default=None, choices=[0, 1, 2, 3, 4], help="A/B: FFM row store policy (kernels.hip top); default = the build's")
     ap.add_argument("--launch-timeout", dest="launch_timeout", type=float, default=900.0,
                     help="self-launched N>1 run (no WORLD_SIZE in the environment): seconds after which the parent ends its ranks and exits non-zero")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline line does not need: the CPU baseline, the config-E / config-B / no-kept-rows legs, the "
+                         "host-fed (pcie_inclusive) rate, the live HBM traffic, the measured copy peak, the CPU oracle's committed curves beside the "
+                         "run's own (oracle_*) and, N>1, the other multi-GPU modes (dp_modes).  The --no-* switches above leave parts of it out; --long "
+                         "is a protocol of its own and reports all of its figures either way")
     ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
                     help="after the timed steps, rank 0 replays the last step's records on a fresh model in the in-order mode and writes its predictions, "
                          "a seeded sample of its tables and a concurrent predict-only pass as DIR/<name>.npy (float32), the same every run")
@@ -848,7 +878,7 @@ def main():
         except Exception:  # a side measurement
             return None
 
-    peak_measured = measured_copy_rate() if (rank == 0 and not use_dist) else None
+    peak_measured = measured_copy_rate() if (args.full and rank == 0 and not use_dist) else None
 
     # ---- N>1: replicas + delta all-reduce (local SGD: the agreed model moves by the mean of the replicas' deltas)
     # Cadence: one exchange per 32 steps (0.5 M examples per GPU, ~150 ms of training); a shorter run still times one
@@ -1008,7 +1038,7 @@ def main():
     # ---- secondary figure, never `value`: the same workload fed from HOST memory through the HogwildTrainer replacement
     # (fwgpu_digest_records: pinned staging, PCIe, device-side translation + learn; hogwild.rs:51-60's boundary)
     pcie = None
-    if rank == 0 and world == 1 and not use_dist and not sync_steps and args.cpu:
+    if args.full and rank == 0 and world == 1 and not use_dist and not sync_steps and args.cpu:
         try:
             n_p = 4 * min(B, 65536)
             precs, poff = gen_records(fw, args, 3_000_000_000, n_p)
@@ -1107,18 +1137,29 @@ def main():
     # measurement of this very command (separate --pmc FETCH_SIZE / WRITE_SIZE passes, gfx950 x2 correction on the
     # read side) committed under profiles/, reported only when the run uses the profiled configuration.
     traffic, traffic_src = None, None
-    if args.traffic and rank == 0 and world == 1 and not use_dist:
+    if args.full and args.traffic and rank == 0 and world == 1 and not use_dist:
         traffic, traffic_src = measure_traffic(args)
 
     if rank == 0:
-        oc = oracle_reference_curves(args, world) if not (sync_steps or use_dist) or (args.nn_layers and args.head == "exact" and not use_dist) else {"seq": {}, "hog16": []}
-        oracle_curve = oc["seq"]
-        same_stream = not (sync_steps or use_dist) or (args.nn_layers and args.head == "exact" and not use_dist)
-        occ = oracle_reference_curves(args, world, cn) if same_stream else {"seq": {}, "hog16": []}  # ... on the checkpoints' prefix of the hold-out
+        oracle = {}
+        if args.full:
+            oc = oracle_reference_curves(args, world) if not (sync_steps or use_dist) or (args.nn_layers and args.head == "exact" and not use_dist) else {"seq": {}, "hog16": []}
+            oracle_curve = oc["seq"]
+            same_stream = not (sync_steps or use_dist) or (args.nn_layers and args.head == "exact" and not use_dist)
+            occ = oracle_reference_curves(args, world, cn) if same_stream else {"seq": {}, "hog16": []}  # ... on the checkpoints' prefix of the hold-out
 
-        def hog16_at(n, which=None):  # the 16-thread hogwild oracle's runs at n examples (None where not precomputed)
-            v = [c.get(n) for c in (which or oc)["hog16"] if c.get(n) is not None]
-            return v or None
+            def hog16_at(n, which=None):  # the 16-thread hogwild oracle's runs at n examples (None where not precomputed)
+                v = [c.get(n) for c in (which or oc)["hog16"] if c.get(n) is not None]
+                return v or None
+            oracle = {
+                # the sequential CPU oracle (= the reference's single-thread algorithm) on the same stream, same hold-out tail, same number of examples:
+                # null where it was not precomputed (tests/golden/bench_oracle_curve_seq.json: every multiple of 65 536 up to 3.4 M, every 262 144 up to 16.8 M)
+                "oracle_logloss_after_examples": {str(n): occ["seq"].get(n) for n, v in sorted(curve.items())},
+                "oracle_final_logloss": oracle_curve.get((W + K) * B * world),
+                # ... and the oracle in the reference's 16-thread hogwild mode (hogwild.rs:89-103), every committed run
+                "oracle_hogwild16_logloss_after_examples": {str(n): hog16_at(n, occ) for n, v in sorted(curve.items())},
+                "oracle_hogwild16_final_logloss": hog16_at((W + K) * B * world),
+            }
         achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
         out = {
             "metric": "examples/sec + final log-loss, 30-field k=8 FFM, at 1/2/4/8 MI355X",
@@ -1142,13 +1183,7 @@ def main():
             # hold-out checkpoints during the run: on the FIRST `curve_holdout_examples` examples of the hold-out tail (cheap enough to sit inside the timed wall time)
             "curve_holdout_examples": cn,
             "logloss_after_examples": {str(n): v for n, v in sorted(curve.items())},
-            # the sequential CPU oracle (= the reference's single-thread algorithm) on the same stream, same hold-out tail, same number of examples:
-            # null where it was not precomputed (tests/golden/bench_oracle_curve_seq.json: every multiple of 65 536 up to 3.4 M, every 262 144 up to 16.8 M)
-            "oracle_logloss_after_examples": {str(n): occ["seq"].get(n) for n, v in sorted(curve.items())},
-            "oracle_final_logloss": oracle_curve.get((W + K) * B * world),
-            # ... and the oracle in the reference's 16-thread hogwild mode (hogwild.rs:89-103), every committed run
-            "oracle_hogwild16_logloss_after_examples": {str(n): hog16_at(n, occ) for n, v in sorted(curve.items())},
-            "oracle_hogwild16_final_logloss": hog16_at((W + K) * B * world),
+            **oracle,  # (--full)
             "progressive_logloss_per_step": progressive,
             "seconds_to_logloss": {"target": target_ll, "examples": reached[0] if reached else None,
                                    "seconds": (reached[0] / (world * K * B / elapsed)) if reached else None,
@@ -1217,14 +1252,14 @@ def main():
             tb = 8.0 * ((1 << args.ffm_bits) + args.fields * args.k) + 8.0 * (1 << args.bits)
             out["link_bytes_per_example"] = link_bytes_per_example(args, world, nb.n_ffm / max(nb.n, 1), nb.n_lr / max(nb.n, 1), words[W] / max(nb.n, 1),
                                                                    sync_every, tb)
-        if args.config_e and world == 1 and not use_dist and not sync_steps and not args.nn_layers and args.k == 8 and args.cpu:
+        if args.full and args.config_e and world == 1 and not use_dist and not sync_steps and not args.nn_layers and args.k == 8 and args.cpu:
             # (released first: the child allocates its own 28-bit tables)
             out["config_e"] = "pending"
         if pcie is not None:
             out["pcie_inclusive"] = pcie
         if sparse_main:
             out["sparse_exchange"] = sparse_exchange
-        if args.cpu and world == 1:
+        if args.full and args.cpu and world == 1:
             n_cpu = args.cpu_examples or 20000
             try:
                 out["cpu_baseline"] = cpu_baseline(args, n_cpu)
@@ -1233,7 +1268,7 @@ def main():
                                        "sample": f"failed: {e!r}"}
     else:
         out = None
-    if use_dist and dist_rank is not None and not sharded_main and args.other_modes:
+    if args.full and use_dist and dist_rank is not None and not sharded_main and args.other_modes:
         import threading
 
         def bail():  # the legs hang (a collective that never completes): the line as it stands, then out -- on every rank

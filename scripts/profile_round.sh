@@ -1,12 +1,12 @@
 #!/bin/bash
-# Round profile: default bench line, rocprofv3 kernel trace and the two PMC passes of the same command, single-rank RCCL run.
+# Round profile: default bench line with every side figure (--full), rocprofv3 kernel trace and the two PMC passes of the same command, single-rank RCCL run.
 # usage (on the GPU box, from the repo root): bash scripts/profile_round.sh r01b
 set -u
 TAG=${1:-r01}
 R=$PWD
 OUT=$R/gpurun_out
 mkdir -p $OUT
-timeout 900 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 900 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 600 $OUT/${TAG}_bench.json
 # the driver's shape, and the protocol at its stated length (16 Mi examples, three passes)
 timeout 900 python3 bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_shape.json 2> $OUT/${TAG}_bench_driver_shape.err
@@ -25,12 +25,12 @@ python3 scripts/rocprof_summary.py $(find $OUT/${TAG}_trace $OUT/${TAG}_fetch $O
 head -40 $OUT/${TAG}_kernel_rocprofv3.txt
 rm -rf $OUT/${TAG}_trace $OUT/${TAG}_fetch $OUT/${TAG}_write  # (the rocpd databases: tens of MB each; gpurun merges at most 64 MiB back -- round 6 lost a whole evidence run to them)
 # the multi-GPU code paths with ONE rank over RCCL (library communicator): replica exchange + sharded leg, then the sharded step as the timed mode
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python3 bench.py --force-dist --no-cpu-baseline --no-traffic > $OUT/${TAG}_bench_dist1_replica.json 2> $OUT/${TAG}_bench_dist1_replica.err
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python3 bench.py --force-dist --full --no-cpu-baseline --no-traffic > $OUT/${TAG}_bench_dist1_replica.json 2> $OUT/${TAG}_bench_dist1_replica.err
 MASTER_ADDR=127.0.0.1 MASTER_PORT=29545 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python3 bench.py --force-dist --dp-mode sharded --steps 192 --no-cpu-baseline --no-traffic > $OUT/${TAG}_bench_dist1_sharded.json 2> $OUT/${TAG}_bench_dist1_sharded.err
 tail -c 700 $OUT/${TAG}_bench_dist1_replica.json; echo; tail -c 400 $OUT/${TAG}_bench_dist1_sharded.json; echo
 # config E (configs[4]): exact head (the default) and the mini-batched MFMA head
-timeout 600 python3 bench.py --k 16 --nn-layers 2 --batch 8192 --steps 24 --warmup 2 > $OUT/${TAG}_configE_exact.json 2> $OUT/${TAG}_configE_exact.err
-timeout 600 python3 bench.py --k 16 --nn-layers 2 --head minibatch --batch 1024 --steps 192 --warmup 4 --no-cpu-baseline > $OUT/${TAG}_configE_minibatch.json 2> $OUT/${TAG}_configE_minibatch.err
+timeout 600 python3 bench.py --k 16 --nn-layers 2 --batch 8192 --steps 24 --warmup 2 --full > $OUT/${TAG}_configE_exact.json 2> $OUT/${TAG}_configE_exact.err
+timeout 600 python3 bench.py --k 16 --nn-layers 2 --head minibatch --batch 1024 --steps 192 --warmup 4 --full --no-cpu-baseline > $OUT/${TAG}_configE_minibatch.json 2> $OUT/${TAG}_configE_minibatch.err
 tail -c 500 $OUT/${TAG}_configE_exact.json | head -c 300; echo
 # config E under the profiler: kernel trace + the two PMC passes of the exact-head run, and the predict-only (batched head) launches
 cd /tmp

@@ -30,7 +30,7 @@ def _launch(n, *flags, timeout=900):
 
 
 def test_four_ranks_replica_mode_with_the_sparse_and_sharded_legs():
-    d = _launch(RANKS)
+    d = _launch(RANKS, "--full")  # (--full: the dp_modes legs)
     assert d["n_gpus"] == RANKS and d["rccl_ranks"] == RANKS, (d["n_gpus"], d.get("rccl_ranks"))
     assert d["value"] > 0 and 0.3 < d["final_logloss"] < 0.70
     assert "error" not in d.get("dp_modes", {}), d.get("dp_modes")
@@ -61,7 +61,7 @@ def _self_launch(n, *flags, timeout=900, env_extra=None):
 
 
 def test_bench_launches_its_own_four_ranks_when_no_launcher_set_world_size():
-    p = _self_launch(RANKS)
+    p = _self_launch(RANKS, "--full")
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]  # rank 0's line, once
@@ -98,7 +98,7 @@ def test_two_ranks_on_one_device_over_the_real_rccl_fail_fast_and_loudly():
 def test_the_line_carries_dp_modes_when_a_side_leg_hangs():
     """A side leg that never comes back (a collective that does not complete on a first multi-GPU run) must not cost the line: the watchdog prints rank 0's line with
     dp_modes.error and the run ends non-zero (FWGPU_BENCH_HANG_OTHER_MODES makes the legs sleep instead of running)."""
-    p = _self_launch(2, "--other-modes-timeout", "20", timeout=600, env_extra={"FWGPU_BENCH_HANG_OTHER_MODES": "1"})
+    p = _self_launch(2, "--full", "--other-modes-timeout", "20", timeout=600, env_extra={"FWGPU_BENCH_HANG_OTHER_MODES": "1"})
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert lines, (p.stdout[-1000:], p.stderr[-3000:])
     d = json.loads(lines[-1])

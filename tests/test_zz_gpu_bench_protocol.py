@@ -17,8 +17,8 @@ SPREAD = 0.0020
 
 def test_driver_shape_holdout_loss_is_not_behind_the_reference_modes():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-traffic", "--no-config-e",
-                        "--no-config-b"], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-traffic",
+                        "--no-config-e", "--no-config-b"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["config"]["holdout_examples"] == 262144 and d["steps"] == 20 and d["warmup"] == 5
@@ -44,7 +44,8 @@ def test_config_e_concurrent_holdout_against_the_sequential_oracle_two_sided():
     +0.0012 .. +0.0111, mean +0.0058 -- the dense head's 1.55 MB of weights are read-modify-written by all 512 examples in flight, and that is as noisy as it is.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--k", "16", "--nn-layers", "2", "--nn-width", "256", "--head", "exact", "--batch", "8192", "--steps", "24",
-                        "--warmup", "4", "--holdout", "65536", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "4", "--holdout", "65536", "--full", "--no-cpu-baseline", "--no-traffic", "--no-config-e", "--no-config-b"], env=env, capture_output=True, text=True,
+                       timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     ref = d["oracle_final_logloss"]
