@@ -14,7 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FWGPU_LIBRARY") or os.path.join(_HERE, "lib", "libfwgpu.so")
 
 OK = 0
+ERR_INVALID = 1
 ERR_PARSE, ERR_IO, PARSE_FLUSH, PARSE_HOGWILD_LOAD = 6, 7, 100, 101
+FFM_F32, FFM_F16_BUCKETS = 0, 1  # fwgpu_ffm_storage
 OPT_SGD, OPT_ADAGRAD_FLEX, OPT_ADAGRAD_LUT = 100, 200, 300
 WIRING_REGRESSOR, WIRING_FFM_ONLY = 0, 1
 MODE_SEQUENTIAL, MODE_HOGWILD = 0, 1
@@ -215,6 +217,9 @@ def lib():
         "fwgpu_model_save": [C.c_char_p, vp, vp, vp, i32],
         "fwgpu_model_read_header": [C.c_char_p, P(vp), P(vp)],
         "fwgpu_model_load": [C.c_char_p, i32, i32, P(vp), P(vp), P(vp)],
+        "fwgpu_model_load_packed": [C.c_char_p, i32, P(vp), P(vp), P(vp)],
+        "fwgpu_ffm_storage": [vp, P(i32), P(u64)],
+        "fwgpu_set_wiring": [vp, i32],
         "fwgpu_model_convert_inference": [C.c_char_p, C.c_char_p, i32],
         "fwgpu_quantize_ffm_weights": [vp, u64, vp, u64],
         "fwgpu_dequantize_ffm_weights": [vp, u64, vp],

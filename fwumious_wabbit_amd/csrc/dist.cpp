@@ -647,6 +647,7 @@ int sparse_apply_side(fwgpu_dist *d, fwgpu_dist::SparseSide &s, bool ffm, const 
 int make_rank(fwgpu_regressor *r, int rank, int n, fwgpu_dist **out) {
     if (!r || !out || n < 1 || rank < 0 || rank >= n) return fail(FWGPU_ERR_INVALID, "dist: bad rank / size");
     if (r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "dist: the sharded mode does not cover models with a deep head yet");
+    if (int rcp = refuse_packed(r, "dist (multi-GPU training)")) return rcp;
     FWGPU_HIP(hipSetDevice(r->device));
     std::unique_ptr<fwgpu_dist> d(new fwgpu_dist());
     d->r = r;

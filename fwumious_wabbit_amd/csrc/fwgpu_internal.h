@@ -266,6 +266,10 @@ void resolve_row_mode(KernelParams &p, uint32_t threads);  // settles KernelPara
 // Enqueue the example kernel.  grid==1 gives the sequential (in-order) semantics.
 hipError_t launch_example_kernel(const KernelParams &p, int optimizer, bool coherent, uint32_t grid,
                                  uint32_t threads, hipStream_t stream);
+// packed FFM table (f16 bucket numbers, fwgpu_model_load_packed): the predict-only launch, and a range of the table expanded to f32 by the same conversion
+bool packed_shape_ok(uint32_t k, uint32_t F);
+hipError_t launch_packed_predict(const KernelParams &p, float increment, float mn, uint32_t grid, uint32_t threads, hipStream_t stream);
+hipError_t launch_packed_expand(const uint16_t *q, float *out, uint64_t n, float increment, float mn, hipStream_t stream);
 // split pipeline: phase 1 = FWD (gather the owned rows, write the split records), 3 = UPD (updates of the owned rows from the
 // records and the gradients); the MID step (records -> logit -> prediction, general gradient / deep-head input) is its own kernel
 hipError_t launch_example_phase(const KernelParams &p, int optimizer, int phase, uint32_t grid, uint32_t threads, hipStream_t stream);
@@ -383,6 +387,11 @@ struct fwgpu_regressor {
     uint64_t lr_len = 0;   // entries
     uint64_t ffm_len = 0;  // floats
     float *d_lr = nullptr, *d_ffm_w = nullptr, *d_ffm_acc = nullptr;
+    // packed form (fwgpu_model_load_packed): the FFM weights stay the quantised file's f16 bucket numbers, d_ffm_w and d_ffm_acc do not exist
+    uint16_t *d_ffm_q = nullptr;
+    uint64_t ffm_q_bytes = 0;           // bytes of that allocation
+    float q_increment = 0, q_min = 0;   // the file's 8-byte header: w = q_min + f32(bucket) * q_increment
+    bool packed() const { return d_ffm_q != nullptr; }
     int placement_tries = 0;                     // candidate allocations timed for d_ffm_acc (regressor.cpp: place_ffm_acc)
     float placement_ms_lo = 0, placement_ms_hi = 0;  // fastest / slowest pair probe among them
     float placement_ms_single = 0;                    // the same probe on the weight table alone
@@ -551,6 +560,8 @@ uint32_t lr_hash_mask(uint32_t bit_precision);
 uint32_t ffm_hash_mask(uint32_t ffm_bits, uint32_t ffm_k);
 void lut_init(float *lut, float learning_rate, float power_t, float init_acc);
 KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int update);
+int refuse_packed(const fwgpu_regressor *r, const char *what);  // FWGPU_ERR_INVALID on a packed regressor, FWGPU_OK otherwise
+int create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out);
 // the fused learn / predict launch of `b` with every row and LR entry reached in its owner's tables (generic kernel); d_shards: device copy
 int run_batch_peer(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, const PeerShards *d_shards, hipStream_t stream,
                    const PushRings *d_push = nullptr, uint32_t stream_consumers = 0, uint32_t device_share = 1, uint32_t stream_max_consumer_waves = 0, uint32_t n_ranks = 0);

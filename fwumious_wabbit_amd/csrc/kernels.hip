@@ -78,6 +78,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, ui
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
 }
 
+// ---- packed FFM rows (fwgpu_model_load_packed): the table holds the quantised inference file's f16 BUCKET NUMBERS, two bytes per weight, and a
+// predict-only gather turns each into the weight the host's dequantize_ffm (model_file.cpp, quantization.rs:82-98) would have stored:
+// w = min + f32(bucket) * increment -- the conversion is exact, then ONE multiply and ONE add, unfused (bit-identical for every f16 pattern).
+__device__ __forceinline__ float packed_weight(uint32_t bucket16, float increment, float mn) {
+    const _Float16 h = __builtin_bit_cast(_Float16, (unsigned short)bucket16);
+    return __fadd_rn(mn, __fmul_rn((float)h, increment));
+}
+typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+// four consecutive buckets (8 bytes) -> the lane's four weights of a row
+__device__ __forceinline__ f4 packed_weights4(u2 raw, float increment, float mn) {
+    return f4{packed_weight(raw[0] & 0xffffu, increment, mn), packed_weight(raw[0] >> 16, increment, mn),
+              packed_weight(raw[1] & 0xffffu, increment, mn), packed_weight(raw[1] >> 16, increment, mn)};
+}
+
 template <int VEC>
 struct Vec;
 template <>
@@ -2751,7 +2765,13 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 // NN: the deep head (a18) as a phase of the two-chunk instantiation -- config E's CONCURRENT launches: nn_forward between the gather and the sigmoid, nn_backward in front
 // of the table update, every FFM pair and every LR combo slot stepping with its own general gradient.  Two 512-thread workgroups per CU where the generic kernel
 // (which keeps the in-order launches: the parity mode) runs one of 1024 (round 6).
-template <int OPT, bool COH, int MAXR, bool WIN, int NC = 1, int POL = FW_DEFAULT_STORE_POLICY, bool NN = false>
+// PK: the FFM table holds 2-byte buckets (packed_weight above) -- predict-only launches of a packed regressor.  Same lane map as the f32 rows (one lane =
+// four consecutive weights, now ONE 8-byte load), no rows kept for an update that never comes, and FW_UG_PK rows in flight per wave: a row in flight
+// costs two registers instead of four, so the same registers carry the same BYTES in flight at twice the rows.
+#ifndef FW_UG_PK
+#define FW_UG_PK 8
+#endif
+template <int OPT, bool COH, int MAXR, bool WIN, int NC = 1, int POL = FW_DEFAULT_STORE_POLICY, bool NN = false, bool PK = false>
 #ifndef FW_LB_WAVES_WIN  // the window path (config C's updating launches): FOUR waves per SIMD = two workgroups per CU, 128 registers -- room for
 #define FW_LB_WAVES_WIN 4  // 14 (round 4: 20) kept rows per wave; faster AND better than three workgroups with 8 kept rows
 #endif
@@ -2765,6 +2785,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
     const KernelParams &p = kp_fresh();
     static_assert(NC == 1 || MAXR == 0, "resident rows are a single-chunk feature");
     static_assert(!NN || (NC == 2 && WIN && COH), "the head is a phase of the concurrent two-chunk instantiation only");
+    static_assert(!PK || (!COH && !WIN && !NN && MAXR == 0), "packed rows are read by predict-only launches, straight through the gather");
     typedef f4 V;
     constexpr int VEC = 4;
     constexpr int AUX = COH ? kAuxSc1 : kAuxPlain;
@@ -2785,7 +2806,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
     constexpr bool kThin = COH && POL >= 3;  // thinned accumulator traffic on hot rows (store policies 3 and 4)
     constexpr bool kAtom = COH && POL == 4;  // ... as atomic adds of m g^2 (policy 4) instead of stores of acc_read + m g^2 (policy 3)
     constexpr int UA = (WIN && NC == 1) ? FW_UA_WIN : FW_UA;  // accumulator rows in flight per wave in the update phase
-    constexpr int UG = (WIN && NC == 1) ? FW_UG_WIN : FW_UG;  // overflow rows in flight per wave in the gather
+    constexpr int UG = PK ? FW_UG_PK : ((WIN && NC == 1) ? FW_UG_WIN : FW_UG);  // overflow rows in flight per wave in the gather
 #ifndef FW_UO_NN
 #define FW_UO_NN FW_UO
 #endif
@@ -2959,6 +2980,9 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         const uint32_t nk2 = cnt < (uint32_t)MAXR + lk ? cnt : (uint32_t)MAXR + lk;              // rows kept, registers + LDS
         const uint32_t kb = kKeepLast ? hi - nk : lo;                      // the first of them (cnt == 0: lo == hi == 0)
         V rows[MAXR > 0 ? MAXR : 1];
+        // packed rows: the file header's two words, launch constants (launch_packed_predict hands them over in the FFM block's two optimizer
+        // parameters, which a predict-only launch never reads: the argument block keeps its size and every field its place)
+        const float pk_inc = PK ? p.ffm_rate : 0.0f, pk_min = PK ? p.ffm_minus_power_t : 0.0f;
         // The rows parked in LDS go there DIRECTLY (LDS-direct loads: no register in between), issued in the same burst as the register rows' loads instead
         // of two at a time behind them: destination = wave-uniform slot base + lane * 16.  -DFW_PARK_FIRST=1 issues them in FRONT of the register rows' loads.
 #ifndef FW_PARK_ASM
@@ -3103,6 +3127,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             // overflow rows of this range: transient (they are re-read in the update phase)
             for (uint32_t i = kKeepLast ? hi : ((kLdsKeep && FW_PARK_DIRECT) ? lo + nk2 + (nk2 < (uint32_t)MAXR ? (uint32_t)MAXR - nk2 : 0u) : lo + MAXR); i < hi; i += UG) {
                 V r[UG][NC];
+                u2 raw[PK ? UG : 1][NC];  // packed rows: the buckets as loaded; converted where the row is consumed
 #pragma unroll
                 for (int u = 0; u < UG; ++u) {
 #pragma unroll
@@ -3111,13 +3136,20 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                         const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[i + u]);
 #pragma unroll
                         for (int c = 0; c < NC; ++c) {
-                            r[u][c] = Vec<VEC>::template load<AUX_G>(make_rsrc(p.ffm_w + h, R * 4), e0c[c] * 4);
+                            if (PK)  // (lanes beyond the row read zeros through the descriptor, like the f32 rows': they take part in no sum)
+                                raw[PK ? u : 0][c] = __builtin_amdgcn_raw_buffer_load_b64(make_rsrc(reinterpret_cast<const uint16_t *>(p.ffm_w) + h, R * 2), (int)(e0c[c] * 2), 0, AUX_G);
+                            else
+                                r[u][c] = Vec<VEC>::template load<AUX_G>(make_rsrc(p.ffm_w + h, R * 4), e0c[c] * 4);
                         }
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < UG; ++u)
                     if (i + u < hi) {
+                        if (PK) {
+#pragma unroll
+                            for (int c = 0; c < NC; ++c) r[u][c] = packed_weights4(raw[PK ? u : 0][c], pk_inc, pk_min);
+                        }
                         FW_CONSUME(r[u], i + u)
                         // the first lds_keep of them stay in LDS for the update phase (as read HERE, like a register-kept row)
                         if (kLdsKeep && !FW_PARK_DIRECT && inb && i + u - (lo + MAXR) < lk)
@@ -3280,7 +3312,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         if (tid == 0) p.pred[ex] = pr;
         FW_TICK(3);
 
-        const bool do_update = p.update && imp != 0.0f;  // regressor.rs:366 (as the stage phase's StageOut::do_update)
+        const bool do_update = !PK && p.update && imp != 0.0f;  // regressor.rs:366 (as the stage phase's StageOut::do_update)
         if (do_update && g != 0.0f) {
             const bool lr_upd = p.has_lr;
             const float *gx = nullptr, *gpair = nullptr;
@@ -3639,6 +3671,39 @@ hipError_t launch_example_kernel(const KernelParams &p_in, int optimizer, bool c
         return launch_v<4>(p, optimizer, coherent, grid, threads, lds, stream);
     }
     return launch_v<1>(p, optimizer, coherent, grid, threads, lds, stream);
+}
+
+// ------------------------------------------------------------------ packed FFM table (fwgpu_model_load_packed)
+// Predict-only launch on a table of f16 bucket numbers.  The shapes are the v2 kernel's: k % 4 == 0, rows that start where the translator's mask puts
+// them (a multiple of next_pow2(k) buckets: 8-byte aligned), R <= 256 or R <= 512 with a field slot never straddling the two chunks.  Anything else is
+// hipErrorInvalidValue: there is no one-bucket-per-lane form (the regressor is refused at creation, an unaligned entry batch at its launch).
+bool packed_shape_ok(uint32_t k, uint32_t F) {
+    const uint32_t R = k * F;
+    return k != 0 && k % 4 == 0 && (R <= 64 * 4 || (R <= 64 * 4 * 2 && 256 % k == 0));
+}
+hipError_t launch_packed_predict(const KernelParams &p_in, float increment, float mn, uint32_t grid, uint32_t threads, hipStream_t stream) {
+    if (p_in.n_examples == 0) return hipSuccess;
+    KernelParams p = p_in;
+    p.kernel_version = 0;
+    if (p.update || p.nn.n_layers || p.shards || !packed_shape_ok(p.k, p.F) || !uses_resident_kernel(p, threads)) return hipErrorInvalidValue;
+    resolve_row_mode(p, threads);
+    const size_t lds = example_kernel_lds_bytes(p, FWGPU_OPT_SGD);
+    p.ffm_acc = nullptr;
+    p.ffm_rate = increment;        // (read as the two launch constants by the PK instantiations only: fw_example_kernel_r, pk_inc / pk_min)
+    p.ffm_minus_power_t = mn;
+    if (p.R > 64 * 4) return launch_persistent(fw_example_kernel_r<FWGPU_OPT_SGD, false, 0, false, 2, FW_DEFAULT_STORE_POLICY, false, true>, p, grid, threads, lds, stream);
+    return launch_persistent(fw_example_kernel_r<FWGPU_OPT_SGD, false, 0, false, 1, FW_DEFAULT_STORE_POLICY, false, true>, p, grid, threads, lds, stream);
+}
+// a range of the packed table as f32, by the gather's own conversion (fwgpu_table_read / fwgpu_table_checksum)
+__global__ void packed_expand_kernel(const uint16_t *q, float *out, unsigned long long n, float increment, float mn) {
+    for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x)
+        out[i] = packed_weight(q[i], increment, mn);
+}
+hipError_t launch_packed_expand(const uint16_t *q, float *out, uint64_t n, float increment, float mn, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16);
+    hipLaunchKernelGGL(packed_expand_kernel, dim3(blocks), dim3(256), 0, stream, q, out, (unsigned long long)n, increment, mn);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ owner-side apply (dist.cpp fwgpu_dist_*_owner)

@@ -694,6 +694,7 @@ int fwgpu_model_load(const char *path, int device, int immutable, fwgpu_vwmap **
 
         fwgpu_regressor *r = *r_inout;
         const bool own = r == nullptr;
+        if (!own && (rc = fwgpu::refuse_packed(r, "hogwild_load"))) return rc;
         struct Guard {  // frees a regressor created here unless the load completes
             fwgpu_regressor **r;
             bool armed;
@@ -742,6 +743,60 @@ int fwgpu_model_load(const char *path, int device, int immutable, fwgpu_vwmap **
         fill_views(mi.get());
         guard.armed = false;
         *r_inout = r;
+        if (vw_out) *vw_out = vw.release();
+        if (mi_out) *mi_out = mi.release();
+        return FWGPU_OK;
+    } catch (const std::exception &e) {
+        return fail(FWGPU_ERR_FORMAT, e.what());
+    }
+}
+
+// fwgpu_model_load(immutable = 1) with the FFM weights left as f16 buckets on the device (include/fwgpu.h).  The device receives the FFM block of
+// the quantised inference file: as read when the file is one, else as quantize_ffm makes it from the file's f32 weights.
+int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, fwgpu_model_instance **mi_out, fwgpu_regressor **r_out) {
+    if (!path || !r_out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *r_out = nullptr;
+    try {
+        File in;
+        in.f = std::fopen(path, "rb");
+        if (!in.f) return fail(FWGPU_ERR_IO, std::string("cannot open ") + path);
+        std::unique_ptr<fwgpu_vwmap, void (*)(fwgpu_vwmap *)> vw(nullptr, fwgpu_vwmap_free);
+        std::unique_ptr<fwgpu_model_instance> mi;
+        read_header(in, vw, mi);
+        BlobShape s;
+        int rc = shape_from_mi(mi.get(), &s);
+        if (rc) return rc;
+        if (!s.nn_layer_len.empty())
+            return fail(FWGPU_ERR_INVALID, "model_load_packed: models with a deep head are not served from packed weights");
+        if (!s.ffm_len) return fail(FWGPU_ERR_INVALID, "model_load_packed: the model has no FFM block, there is nothing to pack");
+        const uint64_t count = in.u64();
+        if (count != s.elems())
+            return fail(FWGPU_ERR_FORMAT, "Lenghts of weights array in regressor file differ: got " + std::to_string(count) +
+                                              ", expected " + std::to_string(s.elems()));
+        const int file_opt = mi->optimizer;
+        const bool quantized = mi->dequantize_weights == 1;
+        const uint64_t body = blob_body_bytes(file_opt, quantized, s);
+        if (in.remaining() < body) return fail(FWGPU_ERR_FORMAT, "model file: truncated weights");
+        std::vector<uint8_t> src(body);
+        in.need(src.data(), body, "weights");
+        const bool sgd = file_opt == FWGPU_OPT_SGD;
+        std::vector<float> lr_w(s.lr_len);
+        for (uint64_t i = 0; i < s.lr_len; i++) std::memcpy(&lr_w[i], src.data() + (sgd ? 4 : 8) * i, 4);  // SGD: {w}, else {w, acc}
+        const uint8_t *ffm = src.data() + s.lr_len * (sgd ? 4 : 8);
+        std::vector<uint8_t> q;
+        if (!quantized) {
+            quantize_ffm(reinterpret_cast<const float *>(ffm), s.ffm_len, q);
+            ffm = q.data();
+        }
+        mi->optimizer = FWGPU_OPT_SGD;  // persistence.rs:164 (immutable)
+        fwgpu_config cfg;
+        rc = fwgpu_mi_configs(mi.get(), device, &cfg, nullptr, nullptr);
+        if (rc) return rc;
+        fwgpu_regressor *r = nullptr;
+        rc = fwgpu::create_packed(&cfg, lr_w.data(), ffm, &r);
+        if (rc) return rc;
+        fill_views(mi.get());
+        *r_out = r;
         if (vw_out) *vw_out = vw.release();
         if (mi_out) *mi_out = mi.release();
         return FWGPU_OK;

@@ -22,6 +22,12 @@ int fail(int code, const std::string &msg) {
 }
 
 // optimizer.rs:121-144 (host: runs once per block at create time, then lives in HBM)
+// A packed regressor (fwgpu_model_load_packed) predicts and nothing else: everything that would write or train its tables is refused here, by name
+int refuse_packed(const fwgpu_regressor *r, const char *what) {
+    if (!r || !r->packed()) return FWGPU_OK;
+    return fail(FWGPU_ERR_INVALID, std::string(what) + ": the regressor's FFM weights are packed f16 buckets (fwgpu_model_load_packed): it only predicts");
+}
+
 void lut_init(float *lut, float learning_rate, float power_t, float init_acc) {
     const float minus_power_t = -power_t;
     for (uint32_t x = 0; x < (uint32_t)kLutSize; x++) {
@@ -323,7 +329,7 @@ int batch_upload(fwgpu_batch *b, const HostBatch &hb, hipStream_t stream) {
 
 KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int update) {
     KernelParams p{};
-    p.ffm_w = r->d_ffm_w;
+    p.ffm_w = r->packed() ? reinterpret_cast<float *>(r->d_ffm_q) : r->d_ffm_w;  // (packed: read by launch_packed_predict's kernels only, as 2-byte buckets)
     p.ffm_acc = r->d_ffm_acc;
     p.lr = r->d_lr;
     p.lut_lr = r->d_lut_lr;
@@ -514,7 +520,36 @@ static int prepare_launch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int upda
 static int run_batch_by_example(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream);
 static bool head_predict_batched(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update);
 static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_t stream);
+// predict-only launch of a packed regressor: the v2 kernel's shapes only (kernels.hip launch_packed_predict)
+static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream) {
+    if (update) return refuse_packed(r, "an updating launch");
+    if (b->n == 0) return FWGPU_OK;
+    if (b->host_copy) return fail(FWGPU_ERR_INVALID, "packed regressor: an example of more than 4096 entries of a kind is not served");
+    if (!b->aligned4)
+        return fail(FWGPU_ERR_INVALID, "packed regressor: an FFM entry's hash is not a multiple of 4 (rows must start where the translator's mask puts them: hash & fwgpu_ffm_hash_mask)");
+    KernelParams p;
+    uint32_t threads = 0;
+    const int32_t kv = r->launch.kernel_version;
+    r->launch.kernel_version = 0;  // (the packed gather exists in the v2 kernel only)
+    int rc = prepare_launch(r, b, mode, 0, p, threads);
+    r->launch.kernel_version = kv;
+    if (rc) return rc;
+    if (!example_kernel_is_resident(p, threads))
+        return fail(FWGPU_ERR_INVALID, "packed regressor: the launch shape is not served (workgroups of at most 512 threads, at most 2048 FFM features per example)");
+    const uint32_t grid = pick_grid(r, p, mode, threads);
+    if (b->work_ring) {
+        rc = mapped_batch_next_counter(b, stream);
+        if (rc) return rc;
+        p.work = b->work;
+    } else {
+        FWGPU_HIP(hipMemsetAsync(b->work, 0, sizeof(uint32_t), stream));
+    }
+    FWGPU_HIP(launch_packed_predict(p, r->q_increment, r->q_min, grid, threads, stream));
+    return FWGPU_OK;
+}
+
 static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream) {
+    if (r->packed()) return run_batch_packed(r, b, mode, update, stream);
     if (b->n == 0) return FWGPU_OK;
     if (b->host_copy) return run_batch_by_example(r, b, update, stream);  // (an example beyond what the fused kernel stages: see learn_one_chunked)
     if (head_predict_batched(r, b, mode, update)) {
@@ -597,6 +632,7 @@ static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_
 
 int run_batch_peer(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, const PeerShards *d_shards, hipStream_t stream,
                    const PushRings *d_push, uint32_t stream_consumers, uint32_t device_share, uint32_t stream_max_consumer_waves, uint32_t n_ranks) {
+    if (int rcp = refuse_packed(r, "peer-sharded tables")) return rcp;
     if (b->n == 0 && !stream_consumers) return FWGPU_OK;  // (a streaming step launches for an empty batch too: the rank's consumers serve the peers)
     if (r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "peer-sharded tables: models with a deep head are not covered");
     KernelParams p;
@@ -744,7 +780,36 @@ static int place_ffm_acc(fwgpu_regressor *r, size_t fbytes) {
     return FWGPU_OK;
 }
 
-int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) {
+static int create_impl(const fwgpu_config *cfg, const uint8_t *packed_blob, fwgpu_regressor **out);
+int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) { return create_impl(cfg, nullptr, out); }
+
+}  // extern "C"
+
+// The packed form: `blob` is the quantised file's FFM block as it is (8-byte header {f32 increment, f32 min}, then one f16 bucket number per weight),
+// lr_w the LR weights [2^bit_precision].  Neither an f32 weight table nor an accumulator table is ever allocated.
+int fwgpu::create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out) {
+    if (!cfg || !lr_w || !blob || !out) return fail(FWGPU_ERR_INVALID, "create_packed: NULL argument");
+    if (cfg->optimizer != FWGPU_OPT_SGD) return fail(FWGPU_ERR_INVALID, "create_packed: a packed regressor is an immutable (SGD) one");
+    if (!cfg->ffm_k) return fail(FWGPU_ERR_INVALID, "packed regressor: the model has no FFM block, there is nothing to pack");
+    if (!packed_shape_ok(cfg->ffm_k, cfg->ffm_num_fields))
+        return fail(FWGPU_ERR_INVALID, "packed regressor: ffm_k must be a multiple of 4 and a row (ffm_k x fields) at most 256 weights, or at most 512 with ffm_k dividing 256; got ffm_k = " +
+                                           std::to_string(cfg->ffm_k) + ", fields = " + std::to_string(cfg->ffm_num_fields));
+    fwgpu_regressor *r = nullptr;
+    int rc = create_impl(cfg, blob, &r);
+    if (rc) return rc;
+    std::vector<float> tmp(r->lr_len * 2, 0.0f);
+    for (uint64_t i = 0; i < r->lr_len; i++) tmp[2 * i] = lr_w[i];
+    if (hipMemcpy(r->d_lr, tmp.data(), r->lr_len * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        fwgpu_free(r);
+        return fail(FWGPU_ERR_DEVICE, "create_packed: LR upload failed");
+    }
+    *out = r;
+    return FWGPU_OK;
+}
+
+extern "C" {
+
+static int create_impl(const fwgpu_config *cfg, const uint8_t *packed_blob, fwgpu_regressor **out) {
     if (!cfg || !out) return fail(FWGPU_ERR_INVALID, "fwgpu_create: NULL argument");
     *out = nullptr;
     if (cfg->optimizer != FWGPU_OPT_SGD && cfg->optimizer != FWGPU_OPT_ADAGRAD_FLEX &&
@@ -781,7 +846,15 @@ int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) {
     // (where the LR table lands relative to the FFM tables was measured not to matter: 3.55 ms per launch either way)
     FWGPU_HIP(hipMalloc((void **)&r->d_lr, r->lr_len * 2 * sizeof(float)));
     FWGPU_HIP(hipMemset(r->d_lr, 0, r->lr_len * 2 * sizeof(float)));
-    if (r->ffm_len) {
+    if (r->ffm_len && packed_blob) {
+        // (+128 bytes of slack: the 8-byte vector of a lane beyond the last row's end stays in the allocation even without the descriptor's bound)
+        r->ffm_q_bytes = r->ffm_len * 2 + 128;
+        FWGPU_HIP(hipMalloc((void **)&r->d_ffm_q, r->ffm_q_bytes));
+        memcpy(&r->q_increment, packed_blob, 4);
+        memcpy(&r->q_min, packed_blob + 4, 4);
+        FWGPU_HIP(hipMemset(reinterpret_cast<unsigned char *>(r->d_ffm_q) + r->ffm_len * 2, 0, 128));
+        FWGPU_HIP(hipMemcpy(r->d_ffm_q, packed_blob + 8, r->ffm_len * 2, hipMemcpyHostToDevice));
+    } else if (r->ffm_len) {
         // +64 floats of slack so that a 16 B vector at the very end of the spill-over tail stays in the allocation
         const size_t fbytes = (r->ffm_len + 64) * sizeof(float);
         FWGPU_HIP(hipMalloc((void **)&r->d_ffm_w, fbytes));
@@ -803,7 +876,7 @@ int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) {
     const float a0 = initial_acc(cfg->optimizer, cfg->init_acc_gradient);
     if (a0 != 0.0f) FWGPU_HIP(launch_fill_lr(r->d_lr, r->lr_len, 0.0f, a0, 0));
     const float fa0 = initial_acc(cfg->optimizer, cfg->ffm_init_acc_gradient);
-    if (r->ffm_len && fa0 != 0.0f) FWGPU_HIP(launch_fill(r->d_ffm_acc, r->ffm_len, fa0, 0));
+    if (r->ffm_len && fa0 != 0.0f && !r->packed()) FWGPU_HIP(launch_fill(r->d_ffm_acc, r->ffm_len, fa0, 0));
     FWGPU_HIP(hipDeviceSynchronize());
     *out = r.release();
     return FWGPU_OK;
@@ -819,6 +892,7 @@ int fwgpu_free(fwgpu_regressor *r) {
     (void)hipFree(r->d_lr);
     (void)hipFree(r->d_ffm_w);
     (void)hipFree(r->d_ffm_acc);
+    (void)hipFree(r->d_ffm_q);
     (void)hipFree(r->d_lut_lr);
     (void)hipFree(r->d_lut_ffm);
     (void)hipFree(r->d_nn_w);
@@ -833,6 +907,7 @@ static int nn_init_weights(fwgpu_regressor *r);
 
 int fwgpu_init_weights(fwgpu_regressor *r) {
     if (!r) return fail(FWGPU_ERR_INVALID, "NULL regressor");
+    if (int rcp = refuse_packed(r, "init_weights")) return rcp;
     FWGPU_HIP(hipSetDevice(r->device));
     const fwgpu_config &c = r->cfg;
     // block_lr.rs:97-105
@@ -851,6 +926,7 @@ int fwgpu_init_weights(fwgpu_regressor *r) {
 
 int fwgpu_set_nn(fwgpu_regressor *r, const fwgpu_nn_config *nn) {
     if (!r || !nn) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (int rcp = refuse_packed(r, "set_nn (the deep head)")) return rcp;
     if (r->cfg.wiring != FWGPU_WIRING_REGRESSOR) return fail(FWGPU_ERR_INVALID, "the deep head needs the REGRESSOR wiring");
     if (nn->n_layers == 0 || nn->n_layers > FWGPU_NN_MAX_LAYERS) return fail(FWGPU_ERR_INVALID, "nn: n_layers must be in 1..8");
     if (nn->topology != 1 && nn->topology != 2)
@@ -940,6 +1016,15 @@ static int nn_init_weights(fwgpu_regressor *r) {
     }
     FWGPU_HIP(hipMemcpy(r->d_nn_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     FWGPU_HIP(launch_fill(r->d_nn_acc, r->nn_len, initial_acc(r->cfg.optimizer, r->nn_cfg.nn_init_acc_gradient), 0));
+    return FWGPU_OK;
+}
+
+int fwgpu_set_wiring(fwgpu_regressor *r, int wiring) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL regressor");
+    if (wiring != FWGPU_WIRING_REGRESSOR && wiring != FWGPU_WIRING_FFM_ONLY) return fail(FWGPU_ERR_INVALID, "unknown wiring");
+    if (wiring != FWGPU_WIRING_REGRESSOR && r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "the deep head needs the REGRESSOR wiring");
+    if (wiring == FWGPU_WIRING_FFM_ONLY && !r->cfg.ffm_k) return fail(FWGPU_ERR_INVALID, "FFM_ONLY needs an FFM block");
+    r->cfg.wiring = wiring;
     return FWGPU_OK;
 }
 
@@ -1057,6 +1142,7 @@ static uint32_t chunk_entries(const fwgpu_regressor *r) {
 }
 
 static int learn_one_chunked(fwgpu_regressor *r, const HostBatch &hb, uint32_t e, int update, float *prediction) {
+    if (int rcp = refuse_packed(r, "an example beyond what one workgroup stages (the chunked pipeline)")) return rcp;
     // With a deep head (regressor.rs:191-323) the chunks' partial records still add up -- per-combo LR sums, field sums, corrections, counts -- so MID forms
     // the head's input x from the TOTAL record once, the head runs once on it (a "mini-batch" of one example is the reference's per-example rule: one
     // AdaGrad step per dense weight with this example's gradient, input gradients from the pre-step weights, block_neural.rs:252-340), and every chunk's
@@ -1372,6 +1458,7 @@ extern "C" {
 int fwgpu_learn_batch_sync(fwgpu_regressor *r, fwgpu_batch *b, fwgpu_split *sp, int mode, void *stream_) {
     if (!r || !b || !sp) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (mode != FWGPU_MODE_SEQUENTIAL && mode != FWGPU_MODE_HOGWILD) return fail(FWGPU_ERR_INVALID, "unknown mode");
+    if (int rcp = refuse_packed(r, "learn_batch_sync")) return rcp;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     FWGPU_HIP(hipSetDevice(r->device));
     SplitRanges rg;
@@ -1398,6 +1485,7 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
     if (!r || !cache) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if ((n_lr && !lr) || (n_ffm && !ffm)) return fail(FWGPU_ERR_INVALID, "NULL entry buffer");
     if (r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "the context cache does not cover models with a deep head");
+    if (int rcp = refuse_packed(r, "setup_cache (a device-side context cache)")) return rcp;
     FWGPU_HIP(hipSetDevice(r->device));
     const uint32_t F = r->cfg.ffm_k ? r->cfg.ffm_num_fields : 0, R = F * r->cfg.ffm_k;
     fwgpu_block_cache *c = *cache;
@@ -1647,11 +1735,44 @@ int fwgpu_table_len(fwgpu_regressor *r, int which, uint64_t *n_floats) {
     return FWGPU_OK;
 }
 
+// packed regressor: the FFM tables are not f32 arrays (the weights are buckets, the accumulators do not exist)
+static bool is_ffm_table(int which) { return which == FWGPU_TABLE_FFM_W || which == FWGPU_TABLE_FFM_ACC; }
+
+int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes) {
+    if (!r || !storage || !table_bytes) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *storage = r->packed() ? FWGPU_FFM_F16_BUCKETS : FWGPU_FFM_F32;
+    *table_bytes = r->packed() ? r->ffm_q_bytes : (r->ffm_len ? (r->ffm_len + 64) * sizeof(float) : 0);
+    return FWGPU_OK;
+}
+
+// a range of the packed weight table as the f32 values it stands for, through the device routine that shares the gather's conversion
+static int packed_table_read(fwgpu_regressor *r, uint64_t offset, uint64_t count, float *host_out) {
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    const uint64_t kChunk = 16ull << 20;
+    float *d = nullptr;
+    if (count == 0) return FWGPU_OK;
+    if (hipMalloc((void **)&d, std::min(count, kChunk) * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FWGPU_ERR_OOM, "table_read: no memory for the expanded range");
+    }
+    hipError_t e = hipSuccess;
+    for (uint64_t at = 0; at < count && e == hipSuccess; at += kChunk) {
+        const uint64_t n = std::min(kChunk, count - at);
+        e = launch_packed_expand(r->d_ffm_q + offset + at, d, n, r->q_increment, r->q_min, 0);
+        if (e == hipSuccess) e = hipMemcpy(host_out + at, d, n * sizeof(float), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("table_read (packed): ") + hipGetErrorString(e));
+    return FWGPU_OK;
+}
+
 int fwgpu_table_device_ptr(fwgpu_regressor *r, int which, void **dev_ptr) {
     float *p;
     uint64_t n;
     int rc = table_ptr(r, which, &p, &n);
     if (rc) return rc;
+    if (is_ffm_table(which) && (rc = refuse_packed(r, "table_device_ptr of an FFM table"))) return rc;
     if (!dev_ptr) return fail(FWGPU_ERR_INVALID, "NULL argument");
     *dev_ptr = p;
     return FWGPU_OK;
@@ -1663,6 +1784,8 @@ int fwgpu_table_read(fwgpu_regressor *r, int which, uint64_t offset, uint64_t co
     int rc = table_ptr(r, which, &p, &n);
     if (rc) return rc;
     if (offset > n || count > n - offset) return fail(FWGPU_ERR_RANGE, "table_read out of range");
+    if (which == FWGPU_TABLE_FFM_ACC && (rc = refuse_packed(r, "table_read of the FFM accumulators"))) return rc;
+    if (which == FWGPU_TABLE_FFM_W && r->packed()) return count && !host_out ? fail(FWGPU_ERR_INVALID, "NULL argument") : packed_table_read(r, offset, count, host_out);
     FWGPU_HIP(hipSetDevice(r->device));
     FWGPU_HIP(hipDeviceSynchronize());
     if (count) FWGPU_HIP(hipMemcpy(host_out, p + offset, count * sizeof(float), hipMemcpyDeviceToHost));
@@ -1675,6 +1798,7 @@ int fwgpu_table_write(fwgpu_regressor *r, int which, uint64_t offset, uint64_t c
     int rc = table_ptr(r, which, &p, &n);
     if (rc) return rc;
     if (offset > n || count > n - offset) return fail(FWGPU_ERR_RANGE, "table_write out of range");
+    if (is_ffm_table(which) && (rc = refuse_packed(r, "table_write of an FFM table"))) return rc;
     FWGPU_HIP(hipSetDevice(r->device));
     FWGPU_HIP(hipDeviceSynchronize());
     if (count) FWGPU_HIP(hipMemcpy(p + offset, host_in, count * sizeof(float), hipMemcpyHostToDevice));
@@ -1686,6 +1810,7 @@ int fwgpu_table_fill(fwgpu_regressor *r, int which, float value) {
     uint64_t n;
     int rc = table_ptr(r, which, &p, &n);
     if (rc) return rc;
+    if (is_ffm_table(which) && (rc = refuse_packed(r, "table_fill of an FFM table"))) return rc;
     FWGPU_HIP(hipSetDevice(r->device));
     FWGPU_HIP(launch_fill(p, n, value, 0));
     FWGPU_HIP(hipDeviceSynchronize());
@@ -1697,13 +1822,28 @@ int fwgpu_table_checksum(fwgpu_regressor *r, int which, uint64_t *checksum) {
     uint64_t n;
     int rc = table_ptr(r, which, &p, &n);
     if (rc) return rc;
+    if (which == FWGPU_TABLE_FFM_ACC && (rc = refuse_packed(r, "table_checksum of the FFM accumulators"))) return rc;
     FWGPU_HIP(hipSetDevice(r->device));
+    float *expanded = nullptr;  // packed weights: the checksum of the f32 values they stand for
+    if (which == FWGPU_TABLE_FFM_W && r->packed()) {
+        if (hipMalloc((void **)&expanded, n * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FWGPU_ERR_OOM, "table_checksum: no memory for the expanded table");
+        }
+        hipError_t ee = launch_packed_expand(r->d_ffm_q, expanded, n, r->q_increment, r->q_min, 0);
+        if (ee != hipSuccess) {
+            (void)hipFree(expanded);
+            return fail(FWGPU_ERR_DEVICE, std::string("checksum: ") + hipGetErrorString(ee));
+        }
+        p = expanded;
+    }
     unsigned long long *d = nullptr;
-    FWGPU_HIP(hipMalloc((void **)&d, sizeof(unsigned long long)));
-    hipError_t e = launch_checksum(p, n, d, 0);
+    hipError_t e = hipMalloc((void **)&d, sizeof(unsigned long long));
+    if (e == hipSuccess) e = launch_checksum(p, n, d, 0);
     unsigned long long h = 0;
     if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
     (void)hipFree(d);
+    (void)hipFree(expanded);
     if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("checksum: ") + hipGetErrorString(e));
     *checksum = h;
     return FWGPU_OK;
@@ -1790,6 +1930,7 @@ int fwgpu_write_weights(fwgpu_regressor *r, uint8_t *buf, uint64_t cap, uint64_t
     uint64_t need = 0;
     int rc = fwgpu_serialized_len(r, &need);
     if (rc) return rc;
+    if ((rc = refuse_packed(r, "write_weights / model_save"))) return rc;
     if (!buf || cap < need) return fail(FWGPU_ERR_RANGE, "write_weights: buffer too small");
     FWGPU_HIP(hipSetDevice(r->device));
     FWGPU_HIP(hipDeviceSynchronize());
@@ -1833,6 +1974,7 @@ int fwgpu_read_weights(fwgpu_regressor *r, const uint8_t *buf, uint64_t len) {
     uint64_t need = 0;
     int rc = fwgpu_serialized_len(r, &need);
     if (rc) return rc;
+    if ((rc = refuse_packed(r, "read_weights / hogwild_load"))) return rc;
     if (!buf || len < need) return fail(FWGPU_ERR_FORMAT, "read_weights: blob shorter than the model");
     uint64_t total = 0;
     memcpy(&total, buf, 8);

@@ -10,7 +10,7 @@
 // of a request in one launch, as records: the kernel's own translation leaves out the namespaces the cache covers
 // (fwgpu_block_cache_cover_record); a request in which some candidate names a context namespace again, or carries a feature
 // equal to a cached one, takes the entry route (host translation + fwgpu_block_cache_filter), which is the reference's rule
-// for those.  Models with a deep head keep the uncached route (whole line scored), which gives the same result.
+// for those.  Models with a deep head, and predictors created with --packed_weights, keep the uncached route (whole line scored), which gives the same result.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -202,14 +202,19 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         if (words[i] == "-i" || words[i] == "--initial_regressor") weights = words[i + 1];
         if (words[i] == "--device") device = std::atoi(words[i + 1].c_str());  // ours: which GPU serves
     }
-    for (const auto &w : words)
+    bool packed = false;
+    for (const auto &w : words) {
         if (w.rfind("--initial_regressor=", 0) == 0) weights = w.substr(std::strlen("--initial_regressor="));
+        if (w == "--packed_weights") packed = true;  // ours: the FFM weights stay f16 buckets on the device (fwgpu_model_load_packed)
+    }
     if (weights.empty()) {
         set_error("Cannot resolve input weights file name");  // the reference panics here (lib.rs:164-167)
         return nullptr;
     }
     auto model = std::make_shared<SharedModel>();
-    if (fwgpu_model_load(weights.c_str(), device, /*immutable=*/1, &model->vw, &model->mi, &model->re) != FWGPU_OK) return nullptr;
+    if ((packed ? fwgpu_model_load_packed(weights.c_str(), device, &model->vw, &model->mi, &model->re)
+                : fwgpu_model_load(weights.c_str(), device, /*immutable=*/1, &model->vw, &model->mi, &model->re)) != FWGPU_OK)
+        return nullptr;
     if (fwgpu_mi_configs(model->mi, device, nullptr, &model->tr, nullptr) != FWGPU_OK) return nullptr;
     auto p = std::make_unique<FfiPredictor>();
     p->model = model;
@@ -249,7 +254,8 @@ float fw_setup_cache(FfiPredictor *ptr, const char *input_buffer) {  // lib.rs:2
     ptr->prefix = nullptr;
     if (fwgpu_parse_prefix_create(ptr->parser, ptr->cached_text.data(), ptr->cached_text.size(), &ptr->prefix) != FWGPU_OK) return kExceptionErrorCode;
     SharedModel &m = *ptr->model;
-    if (m.re->nn.n_layers == 0 && m.re->cfg.ffm_k != 0) {
+    // (a packed regressor keeps no device-side context cache: like a model with a deep head, the whole context + candidate record is scored)
+    if (m.re->nn.n_layers == 0 && m.re->cfg.ffm_k != 0 && !m.re->packed()) {
         // translate_and_filter(buffer, 0, Some(Primitive)) + Regressor::setup_cache (lib.rs:133-146); every namespace this
         // library accepts is primitive (transformed namespaces are refused when the model is loaded)
         float label, imp;

@@ -127,6 +127,7 @@ extern "C" {
 int fwgpu_trainer_create(fwgpu_regressor *r, const fwgpu_translator_config *t, uint32_t micro_batch, fwgpu_trainer **out) {
     if (!r || !t || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (micro_batch == 0) return fail(FWGPU_ERR_INVALID, "micro_batch must be > 0");
+    if (int rcp = refuse_packed(r, "trainer_create")) return rcp;
     int crc = check_translator(r, t);
     if (crc) return crc;
     std::unique_ptr<fwgpu_trainer> tr(new fwgpu_trainer());

@@ -115,11 +115,15 @@ def load_regressor_without_weights(filename: str):
     return ModelInstanceHandle(mi), VwNamespaceMap(_handle=vw)
 
 
-def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0):
-    """persistence.rs:127-174 -> (ModelInstance, VwNamespaceMap, Regressor)"""
+def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0, packed: bool = False):
+    """persistence.rs:127-174 -> (ModelInstance, VwNamespaceMap, Regressor).  packed: an immutable regressor whose FFM weights stay the
+    quantised file's f16 buckets in device memory (fwgpu_model_load_packed): half the table, predict-only"""
     L = capi.lib()
     vw, mih, r = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    capi.check(L.fwgpu_model_load(filename.encode(), device, int(immutable), C.byref(vw), C.byref(mih), C.byref(r)))
+    if packed:
+        capi.check(L.fwgpu_model_load_packed(filename.encode(), device, C.byref(vw), C.byref(mih), C.byref(r)))
+    else:
+        capi.check(L.fwgpu_model_load(filename.encode(), device, int(immutable), C.byref(vw), C.byref(mih), C.byref(r)))
     h = ModelInstanceHandle(mih)
     mi = h.to_model_instance(device)
     h.close()

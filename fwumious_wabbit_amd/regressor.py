@@ -435,6 +435,18 @@ class Regressor:
         """cap on the examples a HOGWILD launch processes concurrently (16 = hogwild.rs's default thread count; 0 = no cap)"""
         check(self.L.fwgpu_set_max_in_flight(self.h, n))
 
+    def set_wiring(self, wiring):
+        """capi.WIRING_REGRESSOR / WIRING_FFM_ONLY on a live regressor (a model file carries no wiring: a loaded regressor starts as REGRESSOR)"""
+        check(self.L.fwgpu_set_wiring(self.h, wiring))
+        self.mi.wiring = wiring
+
+    def ffm_storage(self):
+        """(storage, table_bytes): 0 = f32 FFM weights, 1 = f16 bucket numbers (a packed regressor, persistence.new_regressor_from_filename(packed=True));
+        the bytes the FFM weight table occupies on the device"""
+        st, nb = C.c_int32(0), C.c_uint64(0)
+        check(self.L.fwgpu_ffm_storage(self.h, C.byref(st), C.byref(nb)))
+        return st.value, nb.value
+
     def table_len(self, which):
         n = C.c_uint64(0)
         check(self.L.fwgpu_table_len(self.h, which, C.byref(n)))

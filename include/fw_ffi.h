@@ -5,8 +5,10 @@
  *
  *   lib.rs:150-185  new_fw_predictor_prototype(command)   command = the fw command line; `-i/--initial_regressor FILE` is
  *                                                         loaded as an immutable regressor (persistence.rs:127-174);
- *                                                         `--device N` (ours) picks the GPU.  NULL + fwgpu_last_error() on
- *                                                         failure (the reference panics).
+ *                                                         `--device N` (ours) picks the GPU; `--packed_weights` (ours) keeps
+ *                                                         the FFM weights as the quantised file's f16 buckets on the device
+ *                                                         (fwgpu_model_load_packed: half the table, same calls).  NULL +
+ *                                                         fwgpu_last_error() on failure (the reference panics).
  *   lib.rs:187-205  clone_lite(prototype)                 cheap per-thread copy sharing the weights
  *   lib.rs:207-212  fw_predict(ptr, vw_text)              -> prediction, or -1.0 for EOF / a line that does not parse
  *   lib.rs:224-232  fw_setup_cache(ptr, context_text)     -> 0.0 (or -1.0); remembers the request's context part

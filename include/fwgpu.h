@@ -399,6 +399,9 @@ int fwgpu_trainer_predictions(fwgpu_trainer *tr, float *out, uint64_t cap, uint6
  * threads: workgroup size (multiple of 64, <=1024); workgroups_per_cu: persistent grid = CUs*this.
  * 0 keeps the default.  Does not change results in SEQUENTIAL mode. */
 int fwgpu_set_launch(fwgpu_regressor *r, uint32_t threads, uint32_t workgroups_per_cu);
+/* The graph wiring of a live regressor (a model file carries none: a loaded regressor starts as FWGPU_WIRING_REGRESSOR).  Takes effect at the
+ * next launch; batches made before the call keep their entries. */
+int fwgpu_set_wiring(fwgpu_regressor *r, int wiring);
 /* HOGWILD launches process as many examples concurrently as the device holds workgroups (768 on MI355X at config C).  On a
  * small or tiny-example data set that much staleness keeps the model from learning (hogwild.rs runs 16 threads): n caps
  * the examples in flight, n = 16 is the reference's default degree of concurrency, n = 1 is its single-thread loop (one
@@ -592,6 +595,24 @@ int fwgpu_model_read_header(const char *path, fwgpu_vwmap **vw, fwgpu_model_inst
  * are loaded into the existing regressor.  vw / mi may be NULL. */
 int fwgpu_model_load(const char *path, int device, int immutable, fwgpu_vwmap **vw, fwgpu_model_instance **mi,
                      fwgpu_regressor **r);
+/* fwgpu_model_load(path, device, immutable = 1, ...) whose FFM weights STAY in the quantised inference file's form in device
+ * memory: one f16 bucket number per weight, w = min + f32(bucket) * increment formed inside the predict kernel (bit for bit
+ * what fwgpu_dequantize_ffm_weights gives).  A file with dequantize_weights = true is uploaded as it is; any other model
+ * file is quantised on the host first (what fwgpu_model_convert_inference(..., quantize_weights = 1) would have written).
+ * No f32 FFM table and no accumulator table exist on the device.  The regressor PREDICTS: fwgpu_predict, fwgpu_learn /
+ * fwgpu_learn_batch with update = 0 (entry and record batches, both modes), fwgpu_batch_predictions*, fwgpu_table_len,
+ * fwgpu_table_read / fwgpu_table_checksum of FWGPU_TABLE_FFM_W (the dequantised values).  Everything that would write or
+ * train -- update != 0, fwgpu_learn_batch_sync, fwgpu_table_write / fill / device_ptr on the FFM tables, fwgpu_read_weights,
+ * fwgpu_write_weights, fwgpu_model_save, fwgpu_trainer_create, fwgpu_dist_*, hogwild_load into it -- and fwgpu_setup_cache
+ * return FWGPU_ERR_INVALID and leave it usable.
+ * Refused here with FWGPU_ERR_INVALID: models with a deep head, models without an FFM block, ffm_k % 4 != 0, rows
+ * (ffm_k x fields) of more than 256 weights unless ffm_k divides 256 and the row has at most 512.  Refused at the launch:
+ * entry batches with an FFM hash that is not a multiple of 4 (raw entries that did not pass fwgpu_ffm_hash_mask), examples
+ * of more than 2048 FFM features. */
+int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw, fwgpu_model_instance **mi, fwgpu_regressor **r);
+/* How the FFM weight table lives on the device, and the bytes it occupies there */
+enum { FWGPU_FFM_F32 = 0, FWGPU_FFM_F16_BUCKETS = 1 };
+int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes);
 /* --convert_inference_regressor (main.rs:136-148): training file -> inference file; host only */
 int fwgpu_model_convert_inference(const char *in_path, const char *out_path, int quantize_weights);
 /* quantization.rs:42-98: out = 8-byte header {f32 increment, f32 min} + n f16 bucket numbers (8 + 2n bytes) */
