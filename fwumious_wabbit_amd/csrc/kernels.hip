@@ -1070,7 +1070,8 @@ __device__ __forceinline__ void nn_layer_backward(const DevNN &n, uint32_t l, co
     }
 }
 
-// The same layer backward for HOGWILD launches, where no order is promised: 16-byte device-scope accesses instead of 4-byte
+// The same layer backward in 16-byte accesses -- written for HOGWILD launches, where no order is promised, and taken by every updating launch whose layer
+// shape allows it, the in-order ones included, so that both modes form the input gradient by the same sums: 16-byte device-scope accesses instead of 4-byte
 // ones (a scalar sc1 store is a fabric write of its own, about 6x the time per byte of a 16-byte one: at config E the head
 // issued 388 k of them per example, against 13 k for the whole FFM update), and every thread of the workgroup busy: thread
 // (q, grp) owns input columns 4q .. 4q+3 for the neurons of group grp; the groups' shares of the input gradient meet in LDS.
@@ -1163,13 +1164,20 @@ __device__ __forceinline__ void nn_layer_backward_vec(const DevNN &n, uint32_t l
             else grad_b[i - split] = oe[c];
         }
     }
+    // The other groups add their shares one group after the other, in the order of the groups: a float sum in a FIXED order, so that two launches of the same
+    // shape give the same bits (LDS float atomics, as before, add in the order the groups happen to arrive: the input gradient -- and every LR and FFM step
+    // behind it -- differed in the last bit between any two launches; tests/test_gpu_concurrent_exact.py).  G - 1 barriers: G is 8 at config E's 256-wide layers.
     __syncthreads();
-    if (active && grp != 0) {
+    for (uint32_t gt = 1; gt < G; ++gt) {  // (G is uniform across the workgroup; every turn ends on a barrier, the last one too: the caller may overwrite the sums at once)
+        if (grp == gt) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t i = 4 * q + c;
-            atomicAdd(i < split ? &grad_a[i] : &grad_b[i - split], oe[c]);
+            for (int c = 0; c < 4; ++c) {
+                const uint32_t i = 4 * q + c;
+                float *dst = i < split ? &grad_a[i] : &grad_b[i - split];
+                *dst = *dst + oe[c];
+            }
         }
+        __syncthreads();
     }
     if (has_bias) {
         const size_t ix = (size_t)in * out + tid;
@@ -1206,7 +1214,7 @@ __device__ __forceinline__ void nn_backward(const KernelParams &p, const Lds &s,
     if (tid == 0) b.fg[0] = g;  // og of the single final neuron
     __syncthreads();
     // final neuron: inputs [h_last | x], input gradients -> [h_last (in place) | xg]
-    nn_layer_backward_any<OPT, COH>(n, L, b.fg, b.h + hoff_last, wl, b.x, b.h + hoff_last, b.xg, b.act, tid, bd, p.grid_wgs > 1);
+    nn_layer_backward_any<OPT, COH>(n, L, b.fg, b.h + hoff_last, wl, b.x, b.h + hoff_last, b.xg, b.act, tid, bd, true);
     if (n.topology != 1)
         for (uint32_t i = tid; i < X; i += bd) b.xg[i] = 0.0f;
     __syncthreads();
@@ -1220,11 +1228,11 @@ __device__ __forceinline__ void nn_backward(const KernelParams &p, const Lds &s,
         if (l > 0) {
             const uint32_t pin = n.out[l - 1];
             nn_layer_backward_any<OPT, COH>(n, l, b.m + hoff, b.h + hoff - pin, pin, b.h + hoff - pin, b.h + hoff - pin,
-                                            b.h + hoff - pin, b.act, tid, bd, p.grid_wgs > 1);
+                                            b.h + hoff - pin, b.act, tid, bd, true);
             hoff -= pin;
         } else {
             // first layer: inputs x; its input gradient is ADDED to the copy branch (BlockCopy, block_misc.rs:456-475)
-            nn_layer_backward_any<OPT, COH>(n, 0, b.m + hoff, b.x, X, b.x, b.fg, b.fg, b.act, tid, bd, p.grid_wgs > 1);
+            nn_layer_backward_any<OPT, COH>(n, 0, b.m + hoff, b.x, X, b.x, b.fg, b.fg, b.act, tid, bd, true);
             __syncthreads();
             for (uint32_t i = tid; i < X; i += bd) b.xg[i] = b.fg[i] + b.xg[i];
         }

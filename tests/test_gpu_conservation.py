@@ -148,6 +148,8 @@ class Rig:
             # the hot feature's LR entry (value 1, block_lr.rs:143-147): its accumulator must have grown by sum g_e^2 if every example's g^2 was counted
             lr_acc1 = float(re.table_read(capi.TABLE_LR, 2 * (hh & ((1 << 18) - 1)), 2)[1])
             lr_frac = (lr_acc1 - lr_acc0[q]) / float((ge ** 2).sum()) if self.opt != fw.Optimizer.SGD else float("nan")
+            # (min and max over the row's floats are reported, not asserted: on this rig every float of a row has the SAME gradient.  Where each add lands, per float, is
+            # asserted by tests/test_gpu_concurrent_exact.py test_hot_rows_one_example_in_one / test_hot_rows_default_sampling on rows whose gradients differ per float)
             out.append((float(np.mean(frac)), float(np.min(frac)), float(np.max(frac)), float(len(ge)) / n, lr_frac))
         # the partners never moved: spot-check a row
         assert np.all(re.table_read(capi.TABLE_FFM_W, 20000, 64) == W_PARTNER)
