@@ -21,6 +21,8 @@ OPT_SGD, OPT_ADAGRAD_FLEX, OPT_ADAGRAD_LUT = 100, 200, 300
 WIRING_REGRESSOR, WIRING_FFM_ONLY = 0, 1
 MODE_SEQUENTIAL, MODE_HOGWILD = 0, 1
 TABLE_LR, TABLE_FFM_W, TABLE_FFM_ACC, TABLE_NN_W, TABLE_NN_ACC = 0, 1, 2, 3, 4
+# fwgpu_debug_last_route
+ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK = 0, 1, 2, 3, 4, 5
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
 LR_ENTRY = np.dtype([("hash", "<u4"), ("value", "<f4"), ("combo_index", "<u4")])
@@ -193,6 +195,8 @@ def lib():
         "fwgpu_debug_placement": [vp, P(i32), P(C.c_float), P(C.c_float)],
         "fwgpu_debug_set_kernel_version": [vp, i32],
         "fwgpu_debug_set_option": [vp, i32, i32],
+        "fwgpu_debug_last_route": [vp, P(i32)],
+        "fwgpu_debug_head_inputs": [vp, vp, u64],
         "fwgpu_debug_coherence_probe": [i32, i32, u32, P(u32), P(u32)],
         "fwgpu_debug_head_gemm": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp],
         "fwgpu_synth_records": [P(SynthConfig), u64, u32, vp, u64, vp, P(u64)],

@@ -256,6 +256,7 @@ struct LaunchConfig {
     int32_t wb_flush_every = -1;     // debug option 6: write-back interval of policies 1 / 2 in examples per workgroup (-1: default, 0: never)
     int32_t lds_keep = -1;           // debug option 8: rows per wave kept in LDS beyond the register-kept ones (-1: as many as leave two workgroups per CU)
     int32_t prefetch = 1;            // debug option 7: next-record prefetch of the v2 kernel (A/B runs)
+    int32_t head_predict = -1;       // debug option 14: predict-only batches of a deep head through the batched route (-1: on unless FWGPU_HEAD_PREDICT_PER_EXAMPLE is set)
     bool threads_set = false;
     uint32_t max_in_flight = 0;  // cap on the persistent grid = examples processed concurrently (0: what the device holds)  // fwgpu_set_launch chose the workgroup size: no automatic choice
 };
@@ -408,6 +409,8 @@ struct fwgpu_regressor {
     void *head_scratch = nullptr;  // mini-batched head (head.hip): activations, masks, gradients of the current batch
     float *pred_x = nullptr, *pred_yi = nullptr;  // predict-only batches of a model with a deep head: x [n * X] and {label, importance} [2n] of the batch in flight
     uint32_t pred_cap = 0;
+    uint32_t pred_n = 0;                   // examples whose x the last batched predict launch left in pred_x (0: the last batch launch took another route)
+    int32_t last_route = 0;                // FWGPU_ROUTE_* of the last fwgpu_learn_batch (fwgpu_debug_last_route)
     // scratch for single-example calls
     fwgpu_batch *one = nullptr;
     void *pinned = nullptr;

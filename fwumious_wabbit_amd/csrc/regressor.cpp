@@ -548,13 +548,22 @@ static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int up
     return FWGPU_OK;
 }
 
-static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream) {
+// (`route`: where fwgpu_learn_batch records the path the launch took -- fwgpu_debug_last_route; the single-example calls pass none)
+static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream, int32_t *route = nullptr) {
+    if (route) *route = FWGPU_ROUTE_PACKED;
     if (r->packed()) return run_batch_packed(r, b, mode, update, stream);
+    if (route) *route = FWGPU_ROUTE_NONE;
     if (b->n == 0) return FWGPU_OK;
+    if (route) *route = FWGPU_ROUTE_HOST_WALK;
     if (b->host_copy) return run_batch_by_example(r, b, update, stream);  // (an example beyond what the fused kernel stages: see learn_one_chunked)
+    if (route) *route = FWGPU_ROUTE_FUSED;
     if (head_predict_batched(r, b, mode, update)) {
         const int rcb = run_batch_head_predict(r, b, stream);
-        if (rcb != FWGPU_ERR_RANGE) return rcb;  // (a shape the v2 kernel cannot stage: the per-example forward below)
+        if (route) *route = rcb == FWGPU_ERR_RANGE ? FWGPU_ROUTE_HEAD_BATCHED_REFUSED : FWGPU_ROUTE_HEAD_BATCHED;
+        if (rcb != FWGPU_ERR_RANGE) {
+            if (route && rcb == FWGPU_OK) r->pred_n = b->n;
+            return rcb;  // (a shape the v2 kernel cannot stage: the per-example forward below)
+        }
     }
     KernelParams p;
     uint32_t threads = 0;
@@ -580,7 +589,8 @@ static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, h
 // 0.77 MB of weights for 1.2 MFLOP).  Same numbers as the per-example forward up to the order of the f32 sums.
 static constexpr uint32_t kHeadPredictSlab = 32768;
 static bool head_predict_batched(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update) {
-    static const bool off = getenv("FWGPU_HEAD_PREDICT_PER_EXAMPLE") != nullptr;  // A/B runs and tests: the per-example forward for every launch
+    static const bool env_off = getenv("FWGPU_HEAD_PREDICT_PER_EXAMPLE") != nullptr;  // A/B runs: the per-example forward for every launch
+    const bool off = r->launch.head_predict >= 0 ? r->launch.head_predict == 0 : env_off;  // (fwgpu_debug_set_option 14 overrides the environment)
     if (off || update || !r->nn.n_layers || mode != FWGPU_MODE_HOGWILD || b->n < 256 || b->cache || b->emit_T) return false;
     const uint32_t k = r->cfg.ffm_k, R = k * r->cfg.ffm_num_fields;
     return k && k % 4 == 0 && b->aligned4 && (R <= 256 || (R <= 512 && 256 % k == 0)) && r->launch.kernel_version != 1;
@@ -1057,6 +1067,10 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value) {
     case 5:  // FFM row store policy of hogwild launches: 0 write-through, 1 weights write-back, 2 both tables write-back, -1 the build's default
         if (value < -1 || value > 4) return fail(FWGPU_ERR_INVALID, "store policy option: -1, 0, 1, 2, 3 or 4");
         r->launch.store_policy = value;
+        return FWGPU_OK;
+    case 14:  // predict-only batches of a model with a deep head: 1 / -1 = the batched route where head_predict_batched allows it (default), 0 = the per-example forward for every launch
+        if (value < -1 || value > 1) return fail(FWGPU_ERR_INVALID, "batched head predict option: -1, 0 or 1");
+        r->launch.head_predict = value;
         return FWGPU_OK;
     case 13:  // rows kept from the gather in the large-table kernel: 0 = none (every row re-read by the update: no last-writer-wins over an example's lifetime), 1 / -1 = kept (default)
         if (value < -1 || value > 1) return fail(FWGPU_ERR_INVALID, "kept-rows option: -1, 0 or 1");
@@ -1692,7 +1706,25 @@ int fwgpu_learn_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, 
     if (!r || !b) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (b->owner != r) return fail(FWGPU_ERR_INVALID, "batch belongs to another regressor");
     if (mode != FWGPU_MODE_SEQUENTIAL && mode != FWGPU_MODE_HOGWILD) return fail(FWGPU_ERR_INVALID, "unknown mode");
-    return run_batch(r, b, mode, update, static_cast<hipStream_t>(stream));
+    r->pred_n = 0;
+    r->last_route = FWGPU_ROUTE_NONE;
+    return run_batch(r, b, mode, update, static_cast<hipStream_t>(stream), &r->last_route);
+}
+
+int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route) {
+    if (!r || !route) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *route = r->last_route;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats) {
+    if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (r->last_route != FWGPU_ROUTE_HEAD_BATCHED || !r->pred_n || !r->pred_x)
+        return fail(FWGPU_ERR_INVALID, "head_inputs: the regressor's last batch launch was not a batched head predict");
+    if (n_floats > (uint64_t)r->pred_n * r->nn.X) return fail(FWGPU_ERR_RANGE, "head_inputs: more floats than the last launch wrote (n * X)");
+    FWGPU_HIP(hipDeviceSynchronize());  // (the launch may have run on a stream of the caller's)
+    FWGPU_HIP(hipMemcpy(out, r->pred_x, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return FWGPU_OK;
 }
 
 int fwgpu_batch_predictions(fwgpu_batch *b, float *host_out, uint32_t n, void *stream) {

@@ -414,6 +414,27 @@ class Regressor:
         or on the generic kernel (0) -- fwgpu_debug_set_option 11"""
         check(self.L.fwgpu_debug_set_option(self.h, 11, int(v2)))
 
+    def set_head_predict(self, on):
+        """predict-only HOGWILD batches (256 examples or more) of a model with a deep head: the batched route -- head inputs to a batch buffer, the layers as
+        GEMMs over slabs of examples -- where the shape allows it (1; default -1, which follows FWGPU_HEAD_PREDICT_PER_EXAMPLE) or the per-example forward for
+        every launch (0) -- fwgpu_debug_set_option 14"""
+        check(self.L.fwgpu_debug_set_option(self.h, 14, int(on)))
+
+    def last_route(self):
+        """which path this regressor's last learn_batch took: one of capi.ROUTE_* (fwgpu_debug_last_route)"""
+        route = C.c_int32(-1)
+        check(self.L.fwgpu_debug_last_route(self.h, C.byref(route)))
+        return route.value
+
+    def head_inputs(self, n):
+        """the head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] of the first n examples of the last batched head predict launch, as an
+        (n, X) float32 array; an error if the last learn_batch took another route (fwgpu_debug_head_inputs)"""
+        F = len(self.mi.ffm_fields) if self.mi.ffm_k else 0
+        X = self.mi.num_combos + F * (F + 1) // 2
+        out = np.empty((int(n), X), dtype=np.float32)
+        check(self.L.fwgpu_debug_head_inputs(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
     def set_prefetch(self, on):
         """updating launches copy the next example's record to LDS during the current example (fwgpu_debug_set_option 7; default on)"""
         check(self.L.fwgpu_debug_set_option(self.h, 7, int(bool(on))))

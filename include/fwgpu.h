@@ -465,12 +465,27 @@ int fwgpu_debug_set_kernel_version(fwgpu_regressor *r, int version);
  * option 11: HOGWILD launches of a model with a deep head and rows of 257..512 floats (BASELINE config E: k = 16 at 30 fields): 1 (default, -1) = the head runs
  *   as a phase of the large-table kernel, two 512-thread workgroups per CU, where they fit; 0 = always on the generic kernel (one 1024-thread workgroup per CU).
  *   SEQUENTIAL launches take the generic kernel (the parity mode) unless value 2 forces them onto the large-table kernel too (tests of that kernel's head phase).
+ * option 14: predict-only HOGWILD batches of 256 or more examples of a model with a deep head: 1 (default, -1) = the batched route (the example kernel leaves every example's
+ *   head input in a batch buffer, the layers run as GEMMs over slabs of examples: DESIGN.md 4.4) where the shape allows it; 0 = the per-example forward for every launch.
+ *   -1 follows FWGPU_HEAD_PREDICT_PER_EXAMPLE (set: per example), a value set here overrides it.
  * option 7: value 0 = the updating launches do not prefetch the next example's record (A/B runs; default 1).
  * option 8: rows per wave, beyond the 20 kept in registers, whose gather-time weights are parked in LDS for the update phase instead of
  *   being re-read (config-C-shaped rows on the chained path): 0..3, -1 (default) = as many as still let two workgroups share a CU.
  * (The update path of option 2 = 1 / 2 keeps the first 20 rows of every wave's share of an example from the gather and writes
  *   them back as w_gather - step in HOGWILD launches: what the concurrent mode's hold-out loss rests on) */
 int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value);
+/* Which path the regressor's last fwgpu_learn_batch took (read-only; the single-example calls do not change it): */
+#define FWGPU_ROUTE_NONE 0                 /* no batch launch yet, or an empty batch */
+#define FWGPU_ROUTE_FUSED 1                /* the fused example kernel, the deep head (if any) per example inside it */
+#define FWGPU_ROUTE_HEAD_BATCHED 2         /* predict-only batch of a deep head: head inputs to a batch buffer, layers as GEMMs (option 14) */
+#define FWGPU_ROUTE_HEAD_BATCHED_REFUSED 3 /* ... which refused the batch's shape (FWGPU_ERR_RANGE); the batch was re-run on the fused example kernel, per example */
+#define FWGPU_ROUTE_PACKED 4               /* packed regressor: the packed predict kernel (or its refusal) */
+#define FWGPU_ROUTE_HOST_WALK 5            /* a batch with an oversize example: walked example by example from its host copy */
+int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
+/* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
+ * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED,
+ * FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */
+int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats);
 /* an f32 as serde_json / ryu prints it in the embedded JSON documents ("0.1", "1.0", "1e-7"); NUL-terminated */
 int fwgpu_debug_format_f32(float v, char *buf, uint32_t cap);
 int fwgpu_debug_coherence_probe(int device, int use_sc1, uint32_t iters, uint32_t *stale_words, uint32_t *timeouts);
