@@ -214,6 +214,11 @@ def lib():
         "fwgpu_parse_prefix_is_record": [vp, vp, u32],
         "fwgpu_parser_parse_candidate": [vp, vp, C.c_char_p, u64, vp, u32, P(u32), P(i32)],
         "fwgpu_parser_parse_buffer": [vp, C.c_char_p, u64, vp, u64, vp, u64, P(u64), P(u64), P(u64)],
+        "fwgpu_text_parser_create": [vp, i32, P(vp)],
+        "fwgpu_text_parser_parse_buffer": [vp, C.c_char_p, u64, vp, u64, vp, u64, P(u64), P(u64), P(u64)],
+        "fwgpu_text_parser_last_lines": [vp, P(u64), P(u64)],
+        "fwgpu_record_batch_from_text": [vp, P(TranslatorConfig), vp, C.c_char_p, u64, u64, P(vp), P(u64), P(u64)],
+        "fwgpu_f32_from_text": [C.c_char_p, u64, P(f32), P(i32)],
         "fwgpu_mi_from_json": [C.c_char_p, u64, P(vp)],
         "fwgpu_mi_to_json": [vp, vp, u64, P(u64)],
         "fwgpu_mi_configs": [vp, i32, P(Config), P(TranslatorConfig), P(NNConfig)],
@@ -242,7 +247,7 @@ def lib():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = i32
-    for name in ("fwgpu_vwmap_free", "fwgpu_parser_free", "fwgpu_parse_prefix_free", "fwgpu_cache_free", "fwgpu_mi_free", "fwgpu_input_close"):
+    for name in ("fwgpu_vwmap_free", "fwgpu_parser_free", "fwgpu_text_parser_free", "fwgpu_parse_prefix_free", "fwgpu_cache_free", "fwgpu_mi_free", "fwgpu_input_close"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = None
     for name in ("fwgpu_vwmap_num_namespaces", "fwgpu_vwmap_num_entries"):
@@ -253,6 +258,8 @@ def lib():
         getattr(L, name).restype = i32
     L.fwgpu_parser_command_argument.argtypes = [vp]
     L.fwgpu_parser_command_argument.restype = C.c_char_p
+    L.fwgpu_text_parser_command_argument.argtypes = [vp]
+    L.fwgpu_text_parser_command_argument.restype = C.c_char_p
     L.fwgpu_murmur3_32.argtypes = [C.c_char_p, C.c_size_t, u32]
     L.fwgpu_murmur3_32.restype = u32
     L.fwgpu_lr_hash_mask.argtypes = [u32]

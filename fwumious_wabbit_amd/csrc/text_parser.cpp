@@ -1,0 +1,458 @@
+// Host side of the device text route: VW text goes up in chunks cut at line breaks, textparse.hip turns the lines into the u32 records
+// of parser.rs:57-74, and the lines the kernel does not take are parsed, in order, by the host parser (parser.cpp) -- so every result,
+// stop and message is the host parser's.  Order of a chunk: status kernel -> {status, length} per line to the host -> host parser on
+// the flagged lines, which fixes their lengths and finds the stop -> offsets -> write kernel -> host-parsed records copied in.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "f32_text.h"
+#include "fwgpu_internal.h"
+#include "parser_types.h"
+#include "textparse.h"
+
+namespace fwgpu {
+namespace {
+
+constexpr uint64_t kChunkBytes = 16u << 20;  // text per kernel pass (line positions are u32)
+constexpr size_t kPinnedBytes = 4u << 20;    // staging piece; two of them alternate
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return FWGPU_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        FWGPU_HIP(hipMalloc(&p, want));
+        cap = want;
+        return FWGPU_OK;
+    }
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    template <class T>
+    T *as() const { return static_cast<T *>(p); }
+};
+
+struct HostRecord {
+    uint32_t line;
+    uint64_t off;  // where it goes, in words from the call's first record
+    std::vector<uint32_t> words;
+};
+
+struct TextChunk {  // one chunk of text on the device and what the host knows about its lines
+    DevBuf text, cnt, rank, lstart, status, off, long_list;
+    uint32_t len = 0, nlines = 0, n_used = 0;
+    uint64_t first_word = 0;  // offset of the chunk's first record
+    std::vector<uint2> h_status;
+    std::vector<uint32_t> h_lstart;  // fetched only when a line needs the host or the call stops inside the chunk
+    std::vector<uint64_t> h_off;
+    std::vector<HostRecord> host_recs;
+};
+
+}  // namespace
+}  // namespace fwgpu
+
+using namespace fwgpu;
+
+struct fwgpu_text_parser {
+    fwgpu_parser *host = nullptr;  // takes the lines the kernel flags; owns the command argument
+    int device = 0;
+    hipStream_t stream = nullptr;
+    void *ns_blob = nullptr;
+    TextNsTable ns{};
+    void *pinned[2] = {nullptr, nullptr};
+    hipEvent_t pinned_free[2] = {nullptr, nullptr};
+    uint32_t *long_count = nullptr;
+    DevBuf scan_tmp, words;
+    std::vector<std::unique_ptr<TextChunk>> chunks;
+    std::vector<uint32_t> line_words;  // one host-parsed record
+    uint64_t last_lines = 0, last_host_lines = 0;
+};
+
+namespace fwgpu {
+namespace {
+
+struct RunResult {
+    uint64_t n_records = 0, n_words = 0, consumed = 0;
+    int rc = FWGPU_OK;
+    size_t n_chunks = 0;
+    std::vector<uint64_t> rec_off;  // filled when the caller gave none
+};
+
+int upload_text(fwgpu_text_parser *tp, TextChunk &ch, const char *text, uint32_t len) {
+    int rc = ch.text.ensure((size_t)len + kTextPad + 16);
+    if (rc) return rc;
+    unsigned char *d = ch.text.as<unsigned char>();
+    for (size_t at = 0, k = 0; at < len; at += kPinnedBytes, k ^= 1) {
+        const size_t n = std::min<size_t>(kPinnedBytes, len - at);
+        FWGPU_HIP(hipEventSynchronize(tp->pinned_free[k]));
+        std::memcpy(tp->pinned[k], text + at, n);
+        FWGPU_HIP(hipMemcpyAsync(d + at, tp->pinned[k], n, hipMemcpyHostToDevice, tp->stream));
+        FWGPU_HIP(hipEventRecord(tp->pinned_free[k], tp->stream));
+    }
+    FWGPU_HIP(hipMemsetAsync(d + len, 0, kTextPad, tp->stream));
+    ch.len = len;
+    return FWGPU_OK;
+}
+
+// line index + status pass of a chunk already on the device; leaves h_status
+int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail) {
+    const uint32_t n16 = (ch.len + 15) / 16;
+    int rc = ch.cnt.ensure(4 * ((size_t)n16 + 1));
+    if (!rc) rc = ch.rank.ensure(4 * ((size_t)n16 + 1));
+    const size_t tmp = text_scan_temp_bytes(n16);
+    if (!rc) rc = tp->scan_tmp.ensure(std::max<size_t>(tmp, 256));
+    if (rc) return rc;
+    FWGPU_HIP(text_count_lines(ch.text.as<unsigned char>(), ch.len, ch.cnt.as<uint32_t>(), ch.rank.as<uint32_t>(), tp->scan_tmp.p, tmp, tp->stream));
+    uint32_t newlines = 0;
+    FWGPU_HIP(hipMemcpyAsync(&newlines, ch.rank.as<uint32_t>() + n16, 4, hipMemcpyDeviceToHost, tp->stream));
+    FWGPU_HIP(hipStreamSynchronize(tp->stream));
+    ch.nlines = newlines + (tail ? 1u : 0u);
+    ch.h_lstart.clear();
+    ch.host_recs.clear();
+    ch.n_used = 0;
+    if (!(rc = ch.lstart.ensure(4 * ((size_t)ch.nlines + 2)))) rc = ch.status.ensure(8 * std::max<size_t>(ch.nlines, 1));
+    if (!rc) rc = ch.off.ensure(8 * std::max<size_t>(ch.nlines, 1));
+    if (!rc) rc = ch.long_list.ensure(4 * std::max<size_t>(ch.nlines, 1));
+    if (rc) return rc;
+    FWGPU_HIP(text_line_index(ch.text.as<unsigned char>(), ch.len, ch.rank.as<uint32_t>(), tail ? 1 : 0, ch.lstart.as<uint32_t>(), tp->stream));
+    TextParseArgs a{};
+    a.text = ch.text.as<unsigned char>();
+    a.lstart = ch.lstart.as<uint32_t>();
+    a.nlines = ch.nlines;
+    a.ns = tp->ns;
+    a.status = ch.status.as<uint2>();
+    a.long_list = ch.long_list.as<uint32_t>();
+    a.long_count = tp->long_count;
+    FWGPU_HIP(text_parse_launch(a, false, tp->stream));
+    ch.h_status.resize(ch.nlines);
+    if (ch.nlines) FWGPU_HIP(hipMemcpyAsync(ch.h_status.data(), ch.status.p, 8 * (size_t)ch.nlines, hipMemcpyDeviceToHost, tp->stream));
+    FWGPU_HIP(hipStreamSynchronize(tp->stream));
+    return FWGPU_OK;
+}
+
+int fetch_line_starts(fwgpu_text_parser *tp, TextChunk &ch) {
+    if (!ch.h_lstart.empty()) return FWGPU_OK;
+    ch.h_lstart.resize((size_t)ch.nlines + 1);
+    FWGPU_HIP(hipMemcpyAsync(ch.h_lstart.data(), ch.lstart.p, 4 * ((size_t)ch.nlines + 1), hipMemcpyDeviceToHost, tp->stream));
+    FWGPU_HIP(hipStreamSynchronize(tp->stream));
+    return FWGPU_OK;
+}
+
+// the host parser on one line, exactly as fwgpu_parser_parse_buffer meets it; the record is left in tp->line_words
+int host_line(fwgpu_text_parser *tp, const char *line, uint64_t size) {
+    tp->line_words.resize((size_t)size + tp->ns.num_namespaces + 16);  // a record has at most header + slots + one word per byte
+    uint64_t off2[2], nr = 0, nw = 0, used = 0;
+    int rc = fwgpu_parser_parse_buffer(tp->host, line, size, tp->line_words.data(), tp->line_words.size(), off2, 1, &nr, &nw, &used);
+    if (rc != FWGPU_OK) return rc;
+    if (nr != 1) return fail(FWGPU_ERR_RANGE, "text parser: a record larger than its line allows");
+    tp->line_words.resize((size_t)nw);
+    tp->last_host_lines++;
+    return FWGPU_OK;
+}
+
+// write pass of a chunk: records of its DEVICE_OK lines [0, n_used) to dst + (h_off[line] - rebase)
+int chunk_write(fwgpu_text_parser *tp, TextChunk &ch, uint32_t *dst, uint64_t rebase) {
+    if (!ch.n_used) return FWGPU_OK;
+    if (rebase)
+        for (uint32_t i = 0; i < ch.n_used; i++) ch.h_off[i] -= rebase;
+    FWGPU_HIP(hipMemcpyAsync(ch.off.p, ch.h_off.data(), 8 * (size_t)ch.n_used, hipMemcpyHostToDevice, tp->stream));
+    TextParseArgs a{};
+    a.text = ch.text.as<unsigned char>();
+    a.lstart = ch.lstart.as<uint32_t>();
+    a.nlines = ch.nlines;
+    a.ns = tp->ns;
+    a.status = ch.status.as<uint2>();
+    a.n_used = ch.n_used;
+    a.dst_off = ch.off.as<uint64_t>();
+    a.dst = dst;
+    a.long_list = ch.long_list.as<uint32_t>();
+    a.long_count = tp->long_count;
+    FWGPU_HIP(text_parse_launch(a, true, tp->stream));
+    return FWGPU_OK;
+}
+
+// The walk of fwgpu_parser_parse_buffer over `text`.  keep == false: the records land in `words` (host) chunk by chunk.
+// keep == true: nothing is written yet; the chunks stay on the device (tp->chunks[0 .. n_chunks)) for the caller to place.
+int run(fwgpu_text_parser *tp, const char *text, uint64_t len, uint32_t *words, uint64_t words_cap, uint64_t *rec_off, uint64_t max_records,
+        bool keep, RunResult &R) {
+    FWGPU_HIP(hipSetDevice(tp->device));
+    tp->last_lines = tp->last_host_lines = 0;
+    uint64_t pos = 0, nr = 0, nw = 0;
+    bool stop = false;
+    auto set_off = [&](uint64_t i, uint64_t v) {
+        if (rec_off) rec_off[i] = v;
+        else R.rec_off.push_back(v);
+    };
+    set_off(0, 0);
+    while (pos < len && nr < max_records && !stop) {
+        uint64_t cut = std::min<uint64_t>(len - pos, kChunkBytes);
+        if (pos + cut < len) {  // cut at the last line break of the window
+            const void *nl = memrchr(text + pos, '\n', cut);
+            if (!nl) {  // one line longer than a chunk: the host's
+                const char *e = static_cast<const char *>(std::memchr(text + pos + cut, '\n', len - pos - cut));
+                const uint64_t size = e ? (uint64_t)(e - (text + pos)) + 1 : len - pos;
+                tp->last_lines++;
+                const int rc = host_line(tp, text + pos, size);
+                if (rc != FWGPU_OK) {
+                    R.rc = rc;
+                    break;
+                }
+                if (nw + tp->line_words.size() > words_cap) break;
+                if (keep) {
+                    if (R.n_chunks == tp->chunks.size()) tp->chunks.emplace_back(new TextChunk());
+                    TextChunk &ch = *tp->chunks[R.n_chunks++];
+                    ch.nlines = ch.n_used = ch.len = 0;
+                    ch.host_recs.clear();
+                    ch.host_recs.push_back({0, nw, tp->line_words});
+                } else {
+                    std::memcpy(words + nw, tp->line_words.data(), tp->line_words.size() * 4);
+                }
+                nw += tp->line_words.size();
+                set_off(++nr, nw);
+                pos += size;
+                continue;
+            }
+            cut = (uint64_t)(static_cast<const char *>(nl) - (text + pos)) + 1;
+        }
+        const size_t ci = keep ? R.n_chunks : 0;
+        if (ci == tp->chunks.size()) tp->chunks.emplace_back(new TextChunk());
+        TextChunk &ch = *tp->chunks[ci];
+        if (keep) R.n_chunks++;
+        int rc = upload_text(tp, ch, text + pos, (uint32_t)cut);
+        if (!rc) rc = chunk_status(tp, ch, text[pos + cut - 1] != '\n');
+        if (rc) return rc;
+        ch.first_word = nw;
+        ch.h_off.resize(ch.nlines);
+        uint32_t i = 0;
+        for (; i < ch.nlines; i++) {
+            if (nr == max_records) break;
+            uint64_t reclen = ch.h_status[i].y;
+            tp->last_lines++;
+            if (ch.h_status[i].x != kTextDeviceOk) {
+                if ((rc = fetch_line_starts(tp, ch))) return rc;
+                rc = host_line(tp, text + pos + ch.h_lstart[i], ch.h_lstart[i + 1] - ch.h_lstart[i]);
+                if (rc != FWGPU_OK) {
+                    R.rc = rc;  // a command, or an error with the host parser's message
+                    stop = true;
+                    break;
+                }
+                reclen = tp->line_words.size();
+                if (nw + reclen > words_cap) {
+                    tp->last_lines--;
+                    tp->last_host_lines--;
+                    break;
+                }
+                ch.host_recs.push_back({i, nw, tp->line_words});
+            } else if (nw + reclen > words_cap) {
+                tp->last_lines--;
+                break;
+            }
+            ch.h_off[i] = nw;
+            nw += reclen;
+            set_off(++nr, nw);
+        }
+        ch.n_used = i;
+        if (i < ch.nlines) {  // stopped inside the chunk
+            stop = true;
+            if ((rc = fetch_line_starts(tp, ch))) return rc;
+            pos += ch.h_lstart[i];
+        } else {
+            pos += cut;
+        }
+        if (!keep && nw > ch.first_word) {
+            const uint64_t nwc = nw - ch.first_word;
+            if ((rc = tp->words.ensure(4 * (size_t)nwc))) return rc;
+            if ((rc = chunk_write(tp, ch, tp->words.as<uint32_t>(), ch.first_word))) return rc;
+            FWGPU_HIP(hipMemcpyAsync(words + ch.first_word, tp->words.p, 4 * (size_t)nwc, hipMemcpyDeviceToHost, tp->stream));
+            FWGPU_HIP(hipStreamSynchronize(tp->stream));
+            for (const HostRecord &h : ch.host_recs) std::memcpy(words + h.off, h.words.data(), h.words.size() * 4);
+        }
+    }
+    R.n_records = nr;
+    R.n_words = nw;
+    R.consumed = pos;
+    return FWGPU_OK;
+}
+
+}  // namespace
+}  // namespace fwgpu
+
+extern "C" {
+
+// VowpalParser::new (parser.rs:78-105) for the device route: the vw map's name table, seeds, indices and formats go up once
+int fwgpu_text_parser_create(const fwgpu_vwmap *vw, int device, fwgpu_text_parser **out) {
+    if (!vw || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+        return fail(FWGPU_ERR_DEVICE, "fwgpu_text_parser_create: no such HIP device");
+    std::unique_ptr<fwgpu_text_parser, void (*)(fwgpu_text_parser *)> tp(new fwgpu_text_parser(), fwgpu_text_parser_free);
+    tp->device = device;
+    int rc = fwgpu_parser_create(vw, &tp->host);
+    if (rc) return rc;
+    FWGPU_HIP(hipSetDevice(device));
+    FWGPU_HIP(hipStreamCreateWithFlags(&tp->stream, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) {
+        FWGPU_HIP(hipHostMalloc(&tp->pinned[k], kPinnedBytes, hipHostMallocDefault));
+        FWGPU_HIP(hipEventCreateWithFlags(&tp->pinned_free[k], hipEventDisableTiming));
+    }
+    FWGPU_HIP(hipMalloc((void **)&tp->long_count, 64));
+    const fwgpu_parser &hp = *tp->host;
+    const size_t ne = hp.vw_copy.entries.size(), ns = hp.ns_table.size();
+    std::vector<uint32_t> name_off(ne + 1, 0), seed(ne), index(ne);
+    std::vector<uint8_t> f32(ne);
+    std::string names;
+    for (size_t i = 0; i < ne; i++) {
+        names += hp.vw_copy.entries[i].vwname;
+        name_off[i + 1] = (uint32_t)names.size();
+        seed[i] = hp.seed[i];
+        index[i] = hp.vw_copy.entries[i].index;
+        f32[i] = hp.vw_copy.entries[i].f32;
+    }
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    size_t q = 0;
+    const size_t q_slots = q; q = up(q + 4 * ns);
+    const size_t q_off = q; q = up(q + 4 * (ne + 1));
+    const size_t q_seed = q; q = up(q + 4 * ne);
+    const size_t q_index = q; q = up(q + 4 * ne);
+    const size_t q_f32 = q; q = up(q + ne);
+    const size_t q_names = q; q = up(q + names.size());
+    std::vector<unsigned char> blob(std::max<size_t>(q, 16), 0);
+    std::memcpy(blob.data() + q_slots, hp.ns_table.data(), 4 * ns);
+    std::memcpy(blob.data() + q_off, name_off.data(), 4 * (ne + 1));
+    if (ne) {
+        std::memcpy(blob.data() + q_seed, seed.data(), 4 * ne);
+        std::memcpy(blob.data() + q_index, index.data(), 4 * ne);
+        std::memcpy(blob.data() + q_f32, f32.data(), ne);
+        std::memcpy(blob.data() + q_names, names.data(), names.size());
+    }
+    FWGPU_HIP(hipMalloc(&tp->ns_blob, blob.size()));
+    FWGPU_HIP(hipMemcpy(tp->ns_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    const unsigned char *b = static_cast<const unsigned char *>(tp->ns_blob);
+    tp->ns.slots = reinterpret_cast<const int32_t *>(b + q_slots);
+    tp->ns.name_off = reinterpret_cast<const uint32_t *>(b + q_off);
+    tp->ns.seed = reinterpret_cast<const uint32_t *>(b + q_seed);
+    tp->ns.index = reinterpret_cast<const uint32_t *>(b + q_index);
+    tp->ns.f32 = b + q_f32;
+    tp->ns.names = b + q_names;
+    tp->ns.mask = hp.ns_mask;
+    tp->ns.n_entries = (uint32_t)ne;
+    tp->ns.num_namespaces = hp.vw_copy.num_namespaces;
+    tp->ns.skip_prefix = hp.vw_copy.skip_prefix;
+    *out = tp.release();
+    return FWGPU_OK;
+}
+
+void fwgpu_text_parser_free(fwgpu_text_parser *tp) {
+    if (!tp) return;
+    (void)hipSetDevice(tp->device);
+    if (tp->stream) (void)hipStreamSynchronize(tp->stream);
+    tp->chunks.clear();
+    for (int k = 0; k < 2; k++) {
+        if (tp->pinned[k]) (void)hipHostFree(tp->pinned[k]);
+        if (tp->pinned_free[k]) (void)hipEventDestroy(tp->pinned_free[k]);
+    }
+    if (tp->long_count) (void)hipFree(tp->long_count);
+    if (tp->ns_blob) (void)hipFree(tp->ns_blob);
+    if (tp->stream) (void)hipStreamDestroy(tp->stream);
+    if (tp->host) fwgpu_parser_free(tp->host);
+    delete tp;
+}
+
+// fwgpu_parser_parse_buffer (parser.rs:166-176 over many lines) with the scan of parser.rs:214-461 done by the device
+int fwgpu_text_parser_parse_buffer(fwgpu_text_parser *tp, const char *text, uint64_t len, uint32_t *words, uint64_t words_cap, uint64_t *rec_off,
+                                   uint64_t max_records, uint64_t *n_records, uint64_t *n_words, uint64_t *consumed) {
+    if (!tp || !text || !words || !rec_off || !n_records || !n_words || !consumed) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    RunResult R;
+    int rc = run(tp, text, len, words, words_cap, rec_off, max_records, false, R);
+    if (rc) return rc;
+    *n_records = R.n_records;
+    *n_words = R.n_words;
+    *consumed = R.consumed;
+    return R.rc;
+}
+
+int fwgpu_text_parser_last_lines(const fwgpu_text_parser *tp, uint64_t *lines, uint64_t *host_lines) {
+    if (!tp) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (lines) *lines = tp->last_lines;
+    if (host_lines) *host_lines = tp->last_host_lines;
+    return FWGPU_OK;
+}
+
+// the file name of the last hogwild_load line (parser.rs:149-164), as fwgpu_parser_command_argument
+const char *fwgpu_text_parser_command_argument(const fwgpu_text_parser *tp) { return tp ? fwgpu_parser_command_argument(tp->host) : ""; }
+
+// fwgpu_record_batch_create over the records of `text`, which never come to the host as input: the write kernel puts them into the batch.
+// Stops as fwgpu_parser_parse_buffer stops; a line that is not an example ends the batch before it, and is reported (return code, message,
+// command argument) by the call that finds it first, with no batch.
+int fwgpu_record_batch_from_text(fwgpu_regressor *r, const fwgpu_translator_config *t, fwgpu_text_parser *tp, const char *text, uint64_t len,
+                                 uint64_t max_records, fwgpu_batch **out, uint64_t *n_records, uint64_t *consumed) {
+    if (!r || !t || !tp || !out || !n_records || !consumed || (!text && len)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    *n_records = *consumed = 0;
+    if (r->device != tp->device) return fail(FWGPU_ERR_INVALID, "fwgpu_record_batch_from_text: parser and regressor are on different devices");
+    RunResult R;
+    int rc = run(tp, text ? text : "", len, nullptr, ~0ull, nullptr, std::min<uint64_t>(max_records, 0xffffffffull), true, R);
+    if (rc) return rc;
+    if (R.rc != FWGPU_OK && R.n_records == 0) return R.rc;
+    const uint32_t n = (uint32_t)R.n_records;
+    fwgpu_batch *b = nullptr;
+    rc = record_batch_alloc(r, t, std::max<uint32_t>(n, 1), std::max<uint64_t>(R.n_words, 1), &b);
+    if (rc) return rc;
+    std::vector<uint32_t> back((size_t)R.n_words);
+    auto place = [&]() -> int {
+        for (size_t c = 0; c < R.n_chunks; c++) {
+            TextChunk &ch = *tp->chunks[c];
+            int rc2 = chunk_write(tp, ch, b->records, 0);
+            if (rc2) return rc2;
+            for (const HostRecord &h : ch.host_recs)
+                FWGPU_HIP(hipMemcpyAsync(b->records + h.off, h.words.data(), h.words.size() * 4, hipMemcpyHostToDevice, tp->stream));
+        }
+        FWGPU_HIP(hipMemcpyAsync(b->rec_off, R.rec_off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, tp->stream));
+        // RecordStats and the oversize host copy come from a read-back of the placed records through count_records
+        if (!back.empty()) FWGPU_HIP(hipMemcpyAsync(back.data(), b->records, 4 * back.size(), hipMemcpyDeviceToHost, tp->stream));
+        FWGPU_HIP(hipStreamSynchronize(tp->stream));
+        return FWGPU_OK;
+    };
+    rc = place();
+    RecordStats st;
+    if (rc == FWGPU_OK) rc = count_records(t, back.data(), R.rec_off.data(), n, &st);
+    if (rc == FWGPU_OK) {  // as record_batch_upload leaves a batch
+        b->n = n;
+        b->n_lr = st.tot_lr;
+        b->n_ffm = st.tot_ffm;
+        b->n_words = R.n_words;
+        b->max_lr = r->cfg.wiring == FWGPU_WIRING_FFM_ONLY ? 0 : st.max_lr;
+        b->max_ffm = st.max_ffm;
+        b->max_rec = st.max_rec;
+        b->aligned4 = true;
+        rc = record_batch_host_copy_if_oversize(r, t, b, back.data(), R.rec_off.data(), n);
+    }
+    if (rc) {
+        fwgpu_batch_free(b);
+        return rc;
+    }
+    *out = b;
+    *n_records = n;
+    *consumed = R.consumed;
+    return FWGPU_OK;
+}
+
+// the device's number conversion (f32_text.h), compiled for the host: FWGPU_ERR_PARSE when `s` is not in parse_f32_rust's grammar
+int fwgpu_f32_from_text(const char *s, uint64_t len, float *out, int *proven) {
+    if ((!s && len) || !out || !proven) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    const F32Text r = f32_from_text(reinterpret_cast<const unsigned char *>(s), (size_t)len);
+    *proven = r.proven ? 1 : 0;
+    std::memcpy(out, &r.bits, 4);
+    if (!r.grammar) return fail(FWGPU_ERR_PARSE, "not an f32: " + std::string(s ? s : "", (size_t)len));
+    return FWGPU_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,395 @@
+// VW text -> u32 records on the device (parser.rs:214-461 next_vowpal_to_size, as parser.cpp's parse_head / parse_body mirror it).
+//
+// Line index: 16-byte loads count the '\n' bytes of every 16-byte piece, a rocPRIM scan turns the counts into ranks, a second pass
+// writes line_start[rank + 1] = position + 1.
+//
+// Line -> record: one wavefront per line.  The line is copied to LDS with 16-byte loads (coalesced) and everything after that reads LDS.
+//   1. head (label, importance, first '|'): a handful of bytes, scanned by every lane alike;
+//   2. token starts (a non-space byte after a space) by ballot, compacted into an LDS list;
+//   3. one lane per token: end, first ':', weight, namespace lookup (exact bytes) or murmur3 with the seed of the namespace in force -- the
+//      last '|' token before it, a "last set" scan over the ballot of namespace tokens, carried from one group of 64 tokens to the next;
+//   4. the layout (in-place single features, promotion, slot words) is the reference's state machine over the token list in LDS.
+// The kernel never guesses: whatever is not a plain example it reproduces exactly gets NEEDS_HOST and the host parser takes the line.
+// Lines up to 4 KiB run four waves to a workgroup; longer ones (to 64 KiB) are listed and taken by single-wave workgroups with a larger
+// LDS image.  The same code runs twice: once for {status, length}, once -- when the host has placed the records -- to write them.
+#include <hip/hip_runtime.h>
+#include <cstring>
+#include <rocprim/rocprim.hpp>
+
+#include "f32_text.h"
+#include "textparse.h"
+
+namespace fwgpu {
+
+namespace {
+
+constexpr uint32_t kNotSingle = 1u << 31, kMask31 = ~kNotSingle, kNoFeatures = kNotSingle, kNoLabel = 0xff, kFloatOne = 0x3f800000u;
+constexpr int kHeaderLen = 3;
+constexpr int kShortStage = 4096, kShortTok = 512, kShortWaves = 4;
+constexpr int kLongStage = 65536, kLongTok = 4096;
+
+__device__ inline void wave_sync() {  // LDS written by some lanes of this wave, read by others
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ inline uint32_t murmur3_dev(const unsigned char *d, uint32_t len, uint32_t seed) {
+    const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
+    uint32_t h1 = seed;
+    const uint32_t nb = len >> 2;
+    for (uint32_t i = 0; i < nb; i++) {
+        uint32_t k1 = d[4 * i] | ((uint32_t)d[4 * i + 1] << 8) | ((uint32_t)d[4 * i + 2] << 16) | ((uint32_t)d[4 * i + 3] << 24);
+        k1 *= c1;
+        k1 = (k1 << 15) | (k1 >> 17);
+        k1 *= c2;
+        h1 ^= k1;
+        h1 = (h1 << 13) | (h1 >> 19);
+        h1 = h1 * 5 + 0xe6546b64u;
+    }
+    const unsigned char *t = d + 4 * nb;
+    uint32_t k1 = 0;
+    const uint32_t r = len & 3;
+    if (r >= 3) k1 ^= (uint32_t)t[2] << 16;
+    if (r >= 2) k1 ^= (uint32_t)t[1] << 8;
+    if (r >= 1) {
+        k1 ^= t[0];
+        k1 *= c1;
+        k1 = (k1 << 15) | (k1 >> 17);
+        k1 *= c2;
+        h1 ^= k1;
+    }
+    h1 ^= len;
+    h1 ^= h1 >> 16;
+    h1 *= 0x85ebca6bu;
+    h1 ^= h1 >> 13;
+    h1 *= 0xc2b2ae35u;
+    h1 ^= h1 >> 16;
+    return h1;
+}
+
+// fwgpu_parser::find_ns on the uploaded table: FNV-1a slot, linear probing, exact comparison of the bytes
+__device__ inline int find_ns_dev(const TextNsTable &ns, const unsigned char *s, uint32_t n) {
+    uint32_t h = 2166136261u;
+    for (uint32_t i = 0; i < n; i++) h = (h ^ s[i]) * 16777619u;
+    uint32_t slot = h & ns.mask;
+    for (;;) {
+        const int e = ns.slots[slot];
+        if (e < 0) return -1;
+        const uint32_t a = ns.name_off[e], l = ns.name_off[e + 1] - a;
+        if (l == n) {
+            uint32_t j = 0;
+            while (j < n && ns.names[a + j] == s[j]) j++;
+            if (j == n) return e;
+        }
+        slot = (slot + 1) & ns.mask;
+    }
+}
+
+// a weight / importance / f32 value the kernel may use: in the grammar, proven, finite, not "NONE"
+__device__ inline bool number_dev(const unsigned char *s, uint32_t n, uint32_t *bits) {
+    if (n == 4 && s[0] == 'N' && s[1] == 'O' && s[2] == 'N' && s[3] == 'E') return false;
+    const F32Text r = f32_from_text(s, n);
+    *bits = r.bits;
+    return r.grammar && r.proven && (r.bits & 0x7f800000u) != 0x7f800000u;
+}
+
+struct LineLds {
+    unsigned char *stage;  // 16-byte aligned, STAGE + 32 bytes
+    uint16_t *tok_start;
+    uint8_t *tok_kind;  // 0 namespace, 1 plain feature (both weights 1), 2 weighted feature, 3 feature of an f32 namespace
+    uint32_t *tok_a;    // namespace: entry; feature: hash
+    uint32_t *tok_w;    // feature: bits of ns_weight * weight, or of the f32 value
+    uint32_t *slots;    // [kTextMaxNamespaces]
+};
+
+// One line by one wave.  Returns the status (wave-uniform); *len_out = record length.  WRITE: `dst` is where the record goes.
+template <int TOKCAP, bool WRITE>
+__device__ uint32_t parse_line_wave(const TextParseArgs &a, uint32_t start, uint32_t size, const LineLds &L, uint32_t *dst, uint32_t *len_out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const TextNsTable &ns = a.ns;
+    const uint32_t rowlen = size - 1;  // "ignore last newline byte": the line's last byte only ever answers the one-past reads
+    // ---- stage
+    const uint32_t base = start & ~15u, o = start & 15u, nvec = (o + size + 15u) >> 4;
+    const uint4 *src = reinterpret_cast<const uint4 *>(a.text + base);
+    uint4 *sd = reinterpret_cast<uint4 *>(L.stage);
+    for (uint32_t v = lane; v < nvec; v += 64) sd[v] = src[v];
+    wave_sync();
+    const unsigned char *c = L.stage + o;
+    // ---- head (parser.rs:226-316)
+    const unsigned char c0 = c[0];
+    if (c0 != '1' && c0 != '-' && c0 != '|') return kTextNeedsHost;  // commands and errors
+    const uint32_t label = c0 == '1' ? 1u : c0 == '-' ? 0u : kNoLabel;
+    uint32_t imp = kFloatOne, ie = 0;
+    if (c0 != '|') {
+        while (ie < rowlen && c[ie] != ' ') ie++;
+        while (ie < rowlen && c[ie] == ' ') ie++;
+        if (c[ie] != '|') {
+            const uint32_t is = ie;
+            while (ie < rowlen && c[ie] != ' ') ie++;
+            if (!number_dev(c + is, ie - is, &imp)) return kTextNeedsHost;
+            if (__uint_as_float(imp) < 0.0f) return kTextNeedsHost;
+        }
+    }
+    while (ie < rowlen && c[ie] != '|') ie++;
+    const uint32_t pos = ie;
+    // a line that ends in two spaces makes the reference scan one more, empty, token at the line's last byte
+    if (rowlen >= 2 && rowlen > pos && c[rowlen - 1] == ' ' && c[rowlen - 2] == ' ') return kTextNeedsHost;
+    // ---- token starts
+    uint32_t ntok = 0;
+    for (uint32_t k = pos; k < rowlen; k += 64) {
+        const uint32_t b = k + lane;
+        bool st = false;
+        if (b < rowlen) st = c[b] != ' ' && (b == pos || c[b - 1] == ' ');
+        const unsigned long long m = __ballot(st);
+        const uint32_t idx = ntok + __popcll(m & ((1ull << lane) - 1ull));
+        if (st && idx < (uint32_t)TOKCAP) L.tok_start[idx] = (uint16_t)b;
+        ntok += __popcll(m);
+    }
+    if (ntok > (uint32_t)TOKCAP) return kTextNeedsHost;
+    wave_sync();
+    // ---- one lane per token
+    int carry_ent = -1;
+    uint32_t carry_w = kFloatOne;
+    bool any_bad = false;
+    for (uint32_t g = 0; g < ntok; g += 64) {
+        const uint32_t t = g + lane;
+        const bool valid = t < ntok;
+        bool bad = false, isns = false;
+        uint32_t s = 0, e = 0, ef = 0, wbits = kFloatOne;
+        int ent = -1;
+        if (valid) {
+            s = L.tok_start[t];
+            e = s;
+            bool colon = false;
+            while (e < rowlen && c[e] != ' ') {
+                if (c[e] == ':' && !colon) colon = true, ef = e;
+                e++;
+            }
+            if (!colon) ef = e;
+            isns = c[s] == '|';
+            if (ef != e && !number_dev(c + ef + 1, e - ef - 1, &wbits)) bad = true;
+            if (isns) {
+                ent = find_ns_dev(ns, c + s + 1, ef - s - 1);
+                if (ent < 0) bad = true;  // not predeclared
+            }
+        }
+        const unsigned long long nsmask = __ballot(valid && isns);
+        const unsigned long long below = nsmask & ((2ull << lane) - 1ull);
+        const int srcl = below ? 63 - __clzll((long long)below) : 0;
+        const int got_ent = __shfl(ent, srcl, 64);
+        const uint32_t got_w = __shfl(wbits, srcl, 64);
+        const int my_ent = below ? got_ent : carry_ent;
+        const uint32_t my_nsw = below ? got_w : carry_w;
+        if (nsmask) {
+            const int top = 63 - __clzll((long long)nsmask);
+            carry_ent = __shfl(ent, top, 64);
+            carry_w = __shfl(wbits, top, 64);
+        }
+        if (valid) {
+            uint32_t kind = 0, av = (uint32_t)ent, wv = 0;
+            if (!isns) {
+                if (my_ent < 0) {
+                    bad = true;
+                } else {
+                    av = murmur3_dev(c + s, ef - s, ns.seed[my_ent]) & kMask31;
+                    const float nsw = __uint_as_float(my_nsw), fw = __uint_as_float(wbits);
+                    const float prod = __fmul_rn(nsw, fw);
+                    if (ns.f32[my_ent]) {
+                        kind = 3;
+                        const uint32_t fs = s + ns.skip_prefix;
+                        wv = 0x7fc00000u;  // no value after the prefix: NaN
+                        if (fs > ef) bad = true;
+                        else if (fs != ef && !number_dev(c + fs, ef - fs, &wv)) bad = true;
+                        if (prod != 1.0f) bad = true;
+                    } else {
+                        kind = (nsw == 1.0f && fw == 1.0f) ? 1 : 2;
+                        wv = __float_as_uint(prod);
+                    }
+                }
+            }
+            L.tok_kind[t] = (uint8_t)kind;
+            L.tok_a[t] = av;
+            L.tok_w[t] = wv;
+        }
+        any_bad = any_bad || __ballot(valid && bad) != 0ull;
+    }
+    if (any_bad) return kTextNeedsHost;
+    // ---- layout (parser.rs:318-457), every lane alike; lane 0 stores
+    const uint32_t nns = ns.num_namespaces;
+    for (uint32_t j = lane; j < nns; j += 64) L.slots[j] = kNoFeatures;
+    wave_sync();
+    uint32_t len = kHeaderLen + nns, ns_slot = 0, ns_start = 0, ns_count = 0;
+    auto push = [&](uint32_t x) {
+        if (WRITE && lane == 0) dst[len] = x;
+        len++;
+    };
+    for (uint32_t t = 0; t < ntok; t++) {
+        const uint32_t kind = L.tok_kind[t], av = L.tok_a[t];
+        if (kind == 0) {
+            ns_slot = ns.index[av];
+            ns_count = 0;
+            ns_start = len;
+            continue;
+        }
+        if (kind == 1 && ns_count == 0) {
+            L.slots[ns_slot] = av;
+        } else {
+            const uint32_t cur = L.slots[ns_slot];
+            if (ns_count == 1 && (cur & kNotSingle) == 0) {  // promote the in-place feature
+                push(cur);
+                push(kFloatOne);
+            }
+            push(av);
+            push(L.tok_w[t]);
+            L.slots[ns_slot] = kNotSingle | ((ns_start << 16) + len);
+        }
+        ns_count++;
+    }
+    if (len > 65535u) return kTextNeedsHost;  // the slot word has 16 bits for a position
+    *len_out = len;
+    if (WRITE) {
+        wave_sync();
+        if (lane == 0) {
+            dst[0] = len;
+            dst[1] = label;
+            dst[2] = imp;
+        }
+        for (uint32_t j = lane; j < nns; j += 64) dst[kHeaderLen + j] = L.slots[j];
+    }
+    return kTextDeviceOk;
+}
+
+template <int STAGE, int TOKCAP>
+__device__ inline LineLds carve(unsigned char *p) {
+    LineLds L;
+    L.stage = p;
+    p += STAGE + 32;
+    L.tok_a = reinterpret_cast<uint32_t *>(p);
+    p += 4 * TOKCAP;
+    L.tok_w = reinterpret_cast<uint32_t *>(p);
+    p += 4 * TOKCAP;
+    L.slots = reinterpret_cast<uint32_t *>(p);
+    p += 4 * kTextMaxNamespaces;
+    L.tok_start = reinterpret_cast<uint16_t *>(p);
+    p += 2 * TOKCAP;
+    L.tok_kind = p;
+    return L;
+}
+template <int STAGE, int TOKCAP>
+constexpr int lds_bytes() {
+    return STAGE + 32 + 11 * TOKCAP + 4 * kTextMaxNamespaces;
+}
+
+// WRITE: does this line's record get written, and where
+__device__ inline bool write_target(const TextParseArgs &a, uint32_t line, uint32_t **dst) {
+    if (line >= a.n_used || a.status[line].x != kTextDeviceOk) return false;
+    *dst = a.dst + a.dst_off[line];
+    return true;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(64 * kShortWaves) void text_parse_short(TextParseArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kShortWaves][lds_bytes<kShortStage, kShortTok>()];
+    static_assert(lds_bytes<kShortStage, kShortTok>() % 16 == 0, "wave images stay 16-byte aligned");
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t line = blockIdx.x * kShortWaves + wave;
+    if (line >= a.nlines) return;
+    const uint32_t start = a.lstart[line], size = a.lstart[line + 1] - start;
+    uint32_t *dst = nullptr;
+    if (WRITE && !write_target(a, line, &dst)) return;
+    uint32_t status = kTextNeedsHost, len = 0;
+    if (ns_ok(a.ns) && size >= 1 && size <= (uint32_t)kLongStage) {
+        if (size > (uint32_t)kShortStage) {  // for the single-wave workgroups
+            if (lane == 0) a.long_list[atomicAdd(a.long_count, 1u)] = line;
+            return;
+        }
+        status = parse_line_wave<kShortTok, WRITE>(a, start, size, carve<kShortStage, kShortTok>(lds[wave]), dst, &len);
+    }
+    if (!WRITE && lane == 0) a.status[line] = make_uint2(status, status == kTextDeviceOk ? len : 0u);
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(64) void text_parse_long(TextParseArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[lds_bytes<kLongStage, kLongTok>()];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n = *a.long_count;
+    for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const uint32_t line = a.long_list[k];
+        const uint32_t start = a.lstart[line], size = a.lstart[line + 1] - start;
+        uint32_t *dst = nullptr;
+        if (WRITE && !write_target(a, line, &dst)) continue;
+        uint32_t len = 0;
+        const uint32_t status = parse_line_wave<kLongTok, WRITE>(a, start, size, carve<kLongStage, kLongTok>(lds), dst, &len);
+        if (!WRITE && lane == 0) a.status[line] = make_uint2(status, status == kTextDeviceOk ? len : 0u);
+        wave_sync();  // the next line reuses the image
+    }
+}
+
+// ---- line index
+__device__ inline uint32_t newline_mask16(uint4 v, uint32_t at, uint32_t len) {  // bit j: byte at + j is a '\n' of the text
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t m = 0;
+    for (int q = 0; q < 4; q++)
+        for (int j = 0; j < 4; j++)
+            if (((w[q] >> (8 * j)) & 0xffu) == '\n' && at + 4 * q + j < len) m |= 1u << (4 * q + j);
+    return m;
+}
+
+__global__ void text_count_newlines(const uint4 *text, uint32_t n16, uint32_t len, uint32_t *cnt) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n16) cnt[t] = __popc(newline_mask16(text[t], 16 * t, len));
+    else if (t == n16) cnt[t] = 0;
+}
+
+__global__ void text_line_starts(const uint4 *text, uint32_t n16, uint32_t len, const uint32_t *rank, int tail, uint32_t *lstart) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0) {
+        lstart[0] = 0;
+        if (tail) lstart[rank[n16] + 1] = len;  // a last line without a newline is a line
+    }
+    if (t >= n16) return;
+    uint32_t m = newline_mask16(text[t], 16 * t, len), r = rank[t];
+    while (m) {
+        const int j = __ffs(m) - 1;
+        m &= m - 1;
+        lstart[++r] = 16 * t + j + 1;
+    }
+}
+
+}  // namespace
+
+size_t text_scan_temp_bytes(uint32_t n16_max) {
+    size_t b = 0;
+    (void)rocprim::exclusive_scan(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)n16_max + 1, rocprim::plus<uint32_t>(), (hipStream_t)0);
+    return b;
+}
+
+hipError_t text_count_lines(const unsigned char *text, uint32_t len, uint32_t *cnt, uint32_t *rank, void *tmp, size_t tmp_bytes, hipStream_t stream) {
+    const uint32_t n16 = (len + 15) / 16;
+    text_count_newlines<<<(n16 + 1 + 255) / 256, 256, 0, stream>>>(reinterpret_cast<const uint4 *>(text), n16, len, cnt);
+    hipError_t e = rocprim::exclusive_scan(tmp, tmp_bytes, cnt, rank, 0u, (size_t)n16 + 1, rocprim::plus<uint32_t>(), stream);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t text_line_index(const unsigned char *text, uint32_t len, const uint32_t *rank, int tail, uint32_t *lstart, hipStream_t stream) {
+    const uint32_t n16 = (len + 15) / 16;
+    text_line_starts<<<(n16 + 255) / 256 + 1, 256, 0, stream>>>(reinterpret_cast<const uint4 *>(text), n16, len, rank, tail, lstart);
+    return hipGetLastError();
+}
+
+hipError_t text_parse_launch(const TextParseArgs &a, bool write, hipStream_t stream) {
+    if (a.nlines == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(a.long_count, 0, 4, stream);
+    if (e != hipSuccess) return e;
+    const uint32_t grid = (a.nlines + kShortWaves - 1) / kShortWaves;
+    if (write) {
+        text_parse_short<true><<<grid, 64 * kShortWaves, 0, stream>>>(a);
+        text_parse_long<true><<<256, 64, 0, stream>>>(a);
+    } else {
+        text_parse_short<false><<<grid, 64 * kShortWaves, 0, stream>>>(a);
+        text_parse_long<false><<<256, 64, 0, stream>>>(a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace fwgpu

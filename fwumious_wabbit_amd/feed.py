@@ -139,6 +139,55 @@ class VowpalParser:
             pass
 
 
+class DeviceVowpalParser:
+    """VowpalParser.parse_buffer with the scan on the device (csrc/textparse.hip): same records, stops, codes and messages.  Lines
+    the kernel does not take (commands, errors, numbers it cannot prove correctly rounded, ...) go through the host parser."""
+
+    def __init__(self, vw: VwNamespaceMap, device=0):
+        self.L = capi.lib()
+        self.h = C.c_void_p()
+        capi.check(self.L.fwgpu_text_parser_create(vw.h, device, C.byref(self.h)))
+
+    def parse_buffer(self, text: bytes, max_records=1 << 20, words_cap=None):
+        """(records u32[], rec_off u64[n+1], bytes consumed, status), as VowpalParser.parse_buffer"""
+        words_cap = words_cap or max(1024, len(text))
+        words = np.empty(words_cap + 64 * 1024, dtype=np.uint32)
+        off = np.zeros(max_records + 1, dtype=np.uint64)
+        nr, nw, used = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.L.fwgpu_text_parser_parse_buffer(self.h, text, len(text), capi.ptr(words), words.size, capi.ptr(off),
+                                                   max_records, C.byref(nr), C.byref(nw), C.byref(used))
+        return words[: nw.value].copy(), off[: nr.value + 1].copy(), used.value, rc
+
+    def last_lines(self):
+        """(lines the last call took, lines of those the host parsed)"""
+        n, h = C.c_uint64(), C.c_uint64()
+        capi.check(self.L.fwgpu_text_parser_last_lines(self.h, C.byref(n), C.byref(h)))
+        return n.value, h.value
+
+    def command_argument(self) -> str:
+        """file name of the last hogwild_load line"""
+        return self.L.fwgpu_text_parser_command_argument(self.h).decode()
+
+    def close(self):
+        if self.h:
+            self.L.fwgpu_text_parser_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def f32_from_text(s):
+    """(value, proven) of the device's decimal -> f32 conversion compiled for the host; FwgpuError(ERR_PARSE) outside the grammar"""
+    b = s.encode() if isinstance(s, str) else bytes(s)
+    v, p = C.c_float(), C.c_int()
+    capi.check(capi.lib().fwgpu_f32_from_text(b, len(b), C.byref(v), C.byref(p)))
+    return np.float32(v.value), bool(p.value)
+
+
 class ParsePrefix:
     def __init__(self, parser: VowpalParser, cached: bytes):
         self.L = capi.lib()

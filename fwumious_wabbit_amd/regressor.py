@@ -368,6 +368,17 @@ class Regressor:
                                                rec_off.ctypes.data_as(C.c_void_p), len(rec_off) - 1, C.byref(h)))
         return Batch(self, h)
 
+    def record_batch_from_text(self, translator: FeatureBufferTranslator, dparser, text: bytes, max_records=1 << 32) -> Batch:
+        """VW text -> raw-record batch through a feed.DeviceVowpalParser: the records the device parsed stay in HBM.  The batch
+        holds the examples before the first stop; `batch.consumed` says where in `text` to go on."""
+        h = C.c_void_p()
+        n, used = C.c_uint64(), C.c_uint64()
+        check(self.L.fwgpu_record_batch_from_text(self.h, C.byref(translator.c), dparser.h, text, len(text), max_records,
+                                                  C.byref(h), C.byref(n), C.byref(used)))
+        b = Batch(self, h)
+        b.consumed = used.value
+        return b
+
     def learn_batch(self, batch: Batch, mode=capi.MODE_SEQUENTIAL, update=True, stream=None):
         check(self.L.fwgpu_learn_batch(self.h, batch.h, mode, int(update), stream))
 

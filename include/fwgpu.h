@@ -548,6 +548,32 @@ int fwgpu_parser_parse_buffer(fwgpu_parser *p, const char *text, uint64_t len, u
                               uint64_t *rec_off, uint64_t max_records, uint64_t *n_records, uint64_t *n_words,
                               uint64_t *consumed);
 
+/* ---------------------------------------------------------------- VW text parsed on the device (parser.rs:214-461)
+ * The scan of next_vowpal_to_size runs in HIP kernels (csrc/textparse.hip): line index, one wavefront per line, records laid out
+ * word for word as the host parser lays them out.  A line that is not a plain example the kernel reproduces exactly (a command, an
+ * error, NONE / inf / nan, a number it cannot prove correctly rounded, an undeclared namespace, more than 64 KiB, ...) is parsed by
+ * the host parser instead, so fwgpu_text_parser_parse_buffer is fwgpu_parser_parse_buffer on every input: words, rec_off, counts,
+ * consumed, return code, fwgpu_last_error() and the command argument (fwgpu_text_parser_command_argument).  The text goes up in
+ * chunks cut at line breaks through pinned staging: len is not bounded.  fwgpu_text_parser_last_lines: lines the last call took, and
+ * how many of them the host parsed. */
+typedef struct fwgpu_text_parser fwgpu_text_parser;
+int fwgpu_text_parser_create(const fwgpu_vwmap *vw, int device, fwgpu_text_parser **out);
+void fwgpu_text_parser_free(fwgpu_text_parser *tp);
+int fwgpu_text_parser_parse_buffer(fwgpu_text_parser *tp, const char *text, uint64_t len, uint32_t *words, uint64_t words_cap,
+                                   uint64_t *rec_off, uint64_t max_records, uint64_t *n_records, uint64_t *n_words,
+                                   uint64_t *consumed);
+int fwgpu_text_parser_last_lines(const fwgpu_text_parser *tp, uint64_t *lines, uint64_t *host_lines);
+const char *fwgpu_text_parser_command_argument(const fwgpu_text_parser *tp);
+/* Text -> raw-record batch, as fwgpu_record_batch_create makes from the same records; the records the device parsed never leave
+ * it.  Stops as fwgpu_parser_parse_buffer stops (max_records, a line that is not an example): the batch holds the examples before
+ * the stop and *consumed says where to go on.  A call whose FIRST line is not an example returns that line's code (FWGPU_PARSE_FLUSH,
+ * FWGPU_PARSE_HOGWILD_LOAD, FWGPU_ERR_PARSE) and no batch.  Parser and regressor must be on the same device. */
+int fwgpu_record_batch_from_text(fwgpu_regressor *r, const fwgpu_translator_config *t, fwgpu_text_parser *tp, const char *text,
+                                 uint64_t len, uint64_t max_records, fwgpu_batch **out, uint64_t *n_records, uint64_t *consumed);
+/* The device's decimal -> f32 conversion (csrc/f32_text.h) compiled for the host.  FWGPU_ERR_PARSE: not in Rust's f32::from_str
+ * grammar.  *proven != 0: *out is the correctly rounded value (strtof); otherwise the device leaves the line to the host. */
+int fwgpu_f32_from_text(const char *s, uint64_t len, float *out, int *proven);
+
 /* RecordCache (cache.rs:54-232).  fwgpu_cache_open(input, vw): if "<input>.fwcache" exists and its header ("FWCA",
  * version 11, vw_source equal to `vw`) verifies, the cache is opened for reading; otherwise "<input>.fwcache.writing" is
  * created for writing and renamed by fwgpu_cache_write_finish (cache.rs:70-131, 146-152).  Inputs whose name ends in
