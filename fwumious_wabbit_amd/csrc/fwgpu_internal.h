@@ -183,10 +183,8 @@ struct KernelParams {
                                                        // host side only: workgroups on top of the example workgroups (streaming owner-side apply: the consumers; at least one producer workgroup is kept)
     int32_t kernel_version;             // 0 = auto, 1 = force the v1 kernel, 2 = v2 where applicable
     unsigned long long *ticks;          // optional [8] per-phase shader-clock accumulators (debug), else NULL
-#ifndef FW_KP_NO_CANARY                 // (debug builds of scripts/kp_size_exp.sh drop the two fields: sizeof(KernelParams) 744 -> 728)
     uint32_t *dbg_canary;               // debug (FWGPU_DBG_LDS_CANARY): device counter of LDS canary words found changed, else NULL
     uint32_t dbg_canary_off;            // ... byte offset of the 1 KiB canary behind the kernel's own LDS layout
-#endif
 #ifdef FW_KP_PAD                        // debug builds (scripts/kp_size_exp.sh): the struct's size as a variable of the group-concurrency fault
     unsigned char kp_pad[FW_KP_PAD];
 #endif

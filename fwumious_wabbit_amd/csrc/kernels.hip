@@ -57,10 +57,10 @@
 // that an XCD's L2 is written back every few microseconds whatever the rows' popularity.  All loads stay device-scope (sc1: L1 bypassed, served by
 // the L2 or, for lines another XCD has written through, by the memory side).
 // In-order launches (one workgroup = one XCD) are exact under every policy; the launch's end writes everything back.
-#ifndef FW_DEFAULT_STORE_POLICY
+#ifndef FW_DEFAULT_STORE_POLICY  // the policy of a launch that asks for none, 0..4 as above (profiles/r06_store_policy4_long64_a.txt, profiles/r06_conservation_policy4.txt)
 #define FW_DEFAULT_STORE_POLICY 4
 #endif
-#ifndef FW_DEFAULT_WB_FLUSH_EVERY
+#ifndef FW_DEFAULT_WB_FLUSH_EVERY  // examples between a workgroup's L2 write-backs where the launch sets none (128 against 256: profiles/r04_nt_loads_and_flush256_ab.txt)
 #define FW_DEFAULT_WB_FLUSH_EVERY 128
 #endif
 namespace fwgpu {
@@ -70,6 +70,7 @@ typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 // aux (cache policy) bits of the raw buffer builtins on gfx940+: bit0 sc0, bit1 nt, bit4 sc1.
 constexpr int kAuxPlain = 0;
+constexpr int kAuxNt = 2;   // nt: the L2's streaming replacement policy (still write-back: a hint about WHICH line leaves first)
 constexpr int kAuxSc1 = 16;
 constexpr int kAuxSys = 17;  // sc0 sc1: system scope -- rows in a PEER GPU's memory (peer-sharded tables over xGMI)
 
@@ -813,6 +814,16 @@ size_t example_kernel_lds_bytes(const KernelParams &p, int optimizer) {
 
 
 // ------------------------------------------------------------------ deep head (a18), per-example reference semantics
+// Build-time knobs of the head's layer loops: plain numbers, -DFW_...=N (scripts/build_variant.sh).
+#ifndef FW_NN_FJU  // neurons a wave computes per pass of a layer's forward (eight instead of four since round 5: profiles/r05_configE_generic_kernel_changes_ab.txt)
+#define FW_NN_FJU 8
+#endif
+#ifndef FW_NN_BJU  // neurons whose weights and accumulators a thread has in flight in nn_layer_backward (16 since round 2: profiles/HISTORY.md, "16 neurons in flight per thread in the dense backward")
+#define FW_NN_BJU 16
+#endif
+#ifndef FW_NN_VJU  // active neurons per pass and group in nn_layer_backward_vec (profiles/r05_configE_generic_kernel_changes_ab.txt)
+#define FW_NN_VJU 4
+#endif
 struct NnBuf {
     float *x;    // [X]  inputs: LR slots then triangle (the Join span); BlockCopy output 1 (kept as values)
     float *xg;   // [X]  d logit / d x : through the layers + (topology "one") the final neuron's direct part
@@ -932,9 +943,6 @@ __device__ __forceinline__ float nn_forward(const KernelParams &p, const Lds &s,
         const uint32_t in = n.in[l], out = n.out[l];
         const float *W = n.w + n.off[l];
         // a wave computes JU neurons per pass so that JU * ceil(in / 64) weight loads are in flight per lane
-#ifndef FW_NN_FJU
-#define FW_NN_FJU 8
-#endif
         constexpr int JU = FW_NN_FJU;
         // hogwild launches: the same dot products from 16-byte device-scope loads (4-byte ones run at a third of the rate);
         // the order of the sum differs, which only the in-order mode promises
@@ -1016,9 +1024,6 @@ __device__ __forceinline__ void nn_layer_backward(const DevNN &n, uint32_t l, co
     for (uint32_t i = tid; i < in; i += bd) {
         const float xi = i < split ? in_a[i] : in_b[i - split];
         float oe = 0.0f;
-#ifndef FW_NN_BJU
-#define FW_NN_BJU 16
-#endif
         constexpr int JU = FW_NN_BJU;  // weights (and accumulators) of JU neurons in flight per thread
         for (uint32_t j0 = 0; j0 < out; j0 += JU) {
             float w[JU], a[JU], gg[JU];
@@ -1077,9 +1082,6 @@ __device__ __forceinline__ void nn_layer_backward(const DevNN &n, uint32_t l, co
 // (q, grp) owns input columns 4q .. 4q+3 for the neurons of group grp; the groups' shares of the input gradient meet in LDS.
 // Needs 16-byte aligned rows (in % 4 == 0, layer offset % 4 == 0) and in / 4 <= workgroup size; otherwise the caller keeps
 // nn_layer_backward.  Contains barriers: called by every thread.
-#ifndef FW_NN_VJU
-#define FW_NN_VJU 4
-#endif
 template <int OPT>
 __device__ __forceinline__ void nn_layer_backward_vec(const DevNN &n, uint32_t l, const float *og, const float *in_a,
                                                       uint32_t split, const float *in_b, float *grad_a, float *grad_b,
@@ -1311,8 +1313,21 @@ __device__ __forceinline__ void lr_update(const KernelParams &p, const Lds &s, u
 // Chunks of a row (64 lanes x VEC floats each) whose loads are issued together: rows of up to FW_UPD_CG chunks -- 512 floats at 16 bytes per lane, i.e. config
 // E's 480 -- take ONE memory round trip per batch of U rows instead of one per chunk (round 5: the generic kernel walked the chunks one after the other,
 // 12.5 round trips per wave and example at config E where 6.25 do).
-#ifndef FW_UPD_CG
+// Build-time knobs of the generic kernel, its update and the streaming owner-side apply: plain numbers, -DFW_...=N (scripts/build_variant.sh).
+#ifndef FW_UPD_CG  // chunks of a row whose loads update_rows issues together (profiles/r05_configE_generic_kernel_changes_ab.txt)
 #define FW_UPD_CG 2
+#endif
+#ifndef FW_V1_UG  // feature rows in flight per wave in the generic kernel's gather (2 / 4 / 8 within +-1 %: profiles/HISTORY.md, "Knobs that do not matter any more")
+#define FW_V1_UG 8
+#endif
+#ifndef FW_V1_UU  // ... and in its update, x2 tables (1 / 2 / 3 / 4: profiles/HISTORY.md, "Rows in flight in the generic kernel's update")
+#define FW_V1_UU 2
+#endif
+#ifndef FW_STREAM_KR  // positions of a consumer's stripe polled and stepped per round (profiles/r05_owner_stream_variants_ab.txt)
+#define FW_STREAM_KR 2
+#endif
+#ifndef FW_STREAM_PU  // gradient rows a producer wave has under way at once (profiles/r05_owner_stream_variants_ab.txt)
+#define FW_STREAM_PU 4
 #endif
 template <int VEC, int OPT, int AUX, int U, bool SH = false, int CG = FW_UPD_CG>
 __device__ __forceinline__ void update_rows(const KernelParams &p, const Lds &s, const uint32_t (&idx)[U], float g,
@@ -1684,9 +1699,6 @@ __device__ __forceinline__ void owner_stream_consume(const OwnerStream &os, uint
     const uint32_t lg = os.log2cap_ffm, mask = (1u << lg) - 1u, gmask = lg ? (0xffffffffu >> lg) : 0xffffffffu, R = os.R;
     // KR positions of the stripe per round: their tag words are polled together (lane u loads tag u: one round trip), the rows of those that are there are
     // loaded together (one more), then stepped.  A round waits until each of its positions is either there or beyond the region's final position.
-#ifndef FW_STREAM_KR
-#define FW_STREAM_KR 2
-#endif
     constexpr int KR = FW_STREAM_KR;
     for (uint32_t p0 = os.start_ffm[s] + j;; p0 += KR * J) {
         uint32_t hh[KR];
@@ -1809,12 +1821,6 @@ __global__ void __launch_bounds__(1024) fw_example_kernel(const KernelParams /* 
     constexpr int AUX = COH ? (SH ? kAuxSys : kAuxSc1) : kAuxPlain;
     // a serving context cache (ctx_*, emit_*) only ever comes with read-only launches of the whole kernel, never with the phases of a split step
     constexpr bool kCtx = !COH && PH == 0;
-#ifndef FW_V1_UG
-#define FW_V1_UG 8
-#endif
-#ifndef FW_V1_UU
-#define FW_V1_UU 2
-#endif
     constexpr int UG = FW_V1_UG;  // feature rows in flight per wave in the gather phase
     constexpr int UU = FW_V1_UU;  // feature rows in flight per wave in the update phase (x2 tables)
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1862,10 +1868,8 @@ __global__ void __launch_bounds__(1024) fw_example_kernel(const KernelParams /* 
         hot_lr_init<COH>(p, s, PH == 0);
         s.ctr[kCtrWbCount] = blockIdx.x & 15u;
     }
-#ifndef FW_KP_NO_CANARY
     if (p.dbg_canary)  // debug: 256 words behind this kernel's own LDS layout; nobody may write there
         for (uint32_t i = tid; i < 256; i += bd) reinterpret_cast<uint32_t *>(smem + p.dbg_canary_off)[i] = 0xC0FFEE00u + i;
-#endif
     for (;;) {
         // Previous example's LDS reads are done.  A workgroup-scope barrier does not drain vmcnt on this target,
         // so in the in-order (single workgroup) mode every wave first waits for its own table stores to be
@@ -2213,9 +2217,6 @@ __global__ void __launch_bounds__(1024) fw_example_kernel(const KernelParams /* 
                         }
                     }
                     if (k) {
-#ifndef FW_STREAM_PU
-#define FW_STREAM_PU 4
-#endif
                         constexpr int PU = FW_STREAM_PU;  // gradient rows a wave has under way at once
                         const uint32_t lg = pr.log2cap_ffm, capf = 1u << lg, gmask = lg ? (0xffffffffu >> lg) : 0xffffffffu;
                         // This wave's rows: i = wave, wave + nw, ...  Taken OWNER BY OWNER, so that the wave draws all its positions of an owner's region with one
@@ -2425,11 +2426,9 @@ __global__ void __launch_bounds__(1024) fw_example_kernel(const KernelParams /* 
             }
         }
     }
-#ifndef FW_KP_NO_CANARY
     if (pe.dbg_canary)
         for (uint32_t i = tid_e; i < 256; i += bd_e)
             if (reinterpret_cast<uint32_t *>(smem + pe.dbg_canary_off)[i] != 0xC0FFEE00u + i) atomicAdd(pe.dbg_canary, 1u);
-#endif
 #ifdef FW_TICKS
     if (timing)
         for (int i = 0; i < 8; ++i) atomicAdd(p.ticks + i, tk[i]);
@@ -2576,7 +2575,6 @@ hipError_t launch_example_phase(const KernelParams &p_in, int optimizer, int pha
     size_t lds = example_kernel_lds_bytes(p, optimizer);
     static const bool canary = std::getenv("FWGPU_DBG_LDS_CANARY") != nullptr;
     static uint32_t *d_canary = nullptr;
-#ifndef FW_KP_NO_CANARY
     if (canary) {
         if (!d_canary && (hipMalloc((void **)&d_canary, 4) != hipSuccess || hipMemset(d_canary, 0, 4) != hipSuccess)) return hipErrorOutOfMemory;
         g_dbg_canary = d_canary;
@@ -2584,10 +2582,6 @@ hipError_t launch_example_phase(const KernelParams &p_in, int optimizer, int pha
         p.dbg_canary_off = (uint32_t)lds;
         lds += 1024;
     }
-#else
-    (void)canary;
-    (void)d_canary;
-#endif
     {
         static const char *pad = std::getenv("FWGPU_DBG_LDS_PAD");  // debug: extra dynamic LDS bytes behind the layout (nothing uses them)
         if (pad) lds += (size_t)atoi(pad);
@@ -2715,58 +2709,76 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return v;
 }
 
-#ifndef FW_UG  // rows in flight per wave in the v2 gather
-#define FW_UG 4
-#endif
-#ifndef FW_UA
-#define FW_UA 2
-#endif
-// ... and in the config-C kernel (WIN, single-chunk rows), whose registers go to the rows kept from the gather: 20 kept rows, overflow rows two at a
-// time, accumulator rows one at a time = 128 VGPRs with one spilled; measured (profiles/r04_kept_rows_ab.txt, driver shape / 10 M examples):
+// Build-time knobs of the v2 kernel and its launchers: plain numbers, each overridable with -DFW_...=N (scripts/build_variant.sh).
+// The alternatives that were code paths (keep-last, through-register parking, strided adds, ...) are gone: profiles/HISTORY.md, "Build switches removed".
+//
+// Config-C kernel (WIN, single-chunk rows): its registers go to the rows kept from the gather: 20 kept rows, overflow rows two at a time, accumulator
+// rows one at a time = 128 VGPRs with one spilled; measured (profiles/r04_kept_rows_ab.txt, driver shape / 10 M examples):
 //   kept rows (UG, UA)   14 (4, 2)      16 (4, 2)      18 (2, 2)      20 (2, 1)      22 (2, 1)      24 (2, 1)
 //   examples/s           5.43-5.46 M    5.45-5.49 M    5.45-5.50 M    5.50-5.53 M    5.41-5.43 M    5.28-5.32 M
 //   hold-out after 10 M  0.6299         0.6291         0.6276         0.6233-0.6237  0.6227         0.6224
-// The kept rows' update as branch-free straight-line code with the NEXT row's accumulator load issued before this row's stores (round 4's last
+// The kept rows' update is branch-free straight-line code with the NEXT row's accumulator load issued before this row's stores (round 4's last
 // kernel change: 5.80-5.87 M examples/s against 5.63-5.69 M on one box, `roofline.frac` 0.561-0.568, same loss; profiles/r04_pipelined_update_ab.txt.
 // The same form for the ~5 overflow rows of a wave -- 5 / 8 / 12 static slots with fresh w and acc -- measured 0.6 % SLOWER and is not kept).
-#ifndef FW_PIPE_UPD
-#define FW_PIPE_UPD 1
+#ifndef FW_UG  // overflow rows in flight per wave in the gather (2 / 4 / 8 within +-1 %: profiles/r03_pareto.txt)
+#define FW_UG 4
 #endif
-#ifndef FW_ATOM_COALESCED  // store policy 4: the thinned adds in a layout of their own (256 contiguous bytes per instruction), behind a wave-uniform branch
-#define FW_ATOM_COALESCED 1
+#ifndef FW_UA  // accumulator rows in flight per wave in the kept rows' update (profiles/r03_pareto.txt)
+#define FW_UA 2
+#endif
+#ifndef FW_UG_WIN  // FW_UG of the config-C kernel (profiles/r04_kept_rows_ab.txt, the table above)
+#define FW_UG_WIN 2
+#endif
+#ifndef FW_UA_WIN  // FW_UA of the config-C kernel (profiles/r04_kept_rows_ab.txt)
+#define FW_UA_WIN 1
+#endif
+// PK rows: a row in flight costs two registers instead of four, so the same registers carry the same BYTES in flight at twice the rows
+#ifndef FW_UG_PK  // packed (2-byte bucket) rows in flight per wave in the predict-only gather (profiles/packed_inference.json)
+#define FW_UG_PK 8
+#endif
+#ifndef FW_UO  // overflow rows (w + acc) in flight per wave in the update (2 / 4 / 5 against 1 with the deep head: profiles/r06_configE_v2_head.txt; headless k = 16: profiles/r05_k16_overflow_rows_in_flight_ab.txt)
+#define FW_UO 1
+#endif
+#ifndef FW_PIPE_DEPTH  // rows the accumulator loads of the pipelined kept-row update run ahead, at most (profiles/r04_pipeline_depth_ab.txt)
+#define FW_PIPE_DEPTH 3
 #endif
 // Rows of a wave's range BEYOND the FW_MAXR_WIN register-kept ones whose gather-time w is parked in LDS (Lds::keep) instead of being re-read by the
 // update phase: at most this many per wave; the host grants as many as leave two workgroups on a CU (regressor.cpp prepare_launch, KernelParams::lds_keep).
 // Config C: 55 KB + 3 x 7.7 KB per workgroup -> 3 rows, 23 of ~25 rows per wave written back as w_gather - step; +0.7 % examples/s and 0.002 of hold-out
-// loss after 10 M examples (profiles/r04_parked_rows_ab.txt); a fourth slot that stays empty costs 0.15 %.
-#ifndef FW_LDS_KEEP_MAX
+// loss after 10 M examples; a fourth slot that stays empty costs 0.15 %.
+#ifndef FW_LDS_KEEP_MAX  // rows per wave parked in LDS, at most (profiles/r04_parked_rows_ab.txt)
 #define FW_LDS_KEEP_MAX 3
 #endif
-#ifndef FW_PARK_DIRECT
-#define FW_PARK_DIRECT 1  // the parked rows are loaded with LDS-direct loads in the gather's first burst (0: through registers, two at a time, behind the kept rows)
+#ifndef FW_PARK_ASM  // 1: the parked rows' LDS-direct loads issued through inline asm, in front of the register rows' loads; 0: by the compiler, behind them (profiles/r06_park_asm_ab.txt: +0.5-1.2 % in three of three interleaved pairs)
+#define FW_PARK_ASM 1
 #endif
-#ifndef FW_PIPE_DEPTH
-#define FW_PIPE_DEPTH 3  // rows the accumulator loads of the pipelined kept-row update run ahead, at most
+#ifndef FW_MAXR  // rows per wave kept in registers from the gather to the update, small-table path at six waves per SIMD (profiles/r02_quality_10M.txt)
+#define FW_MAXR 2
 #endif
-#ifndef FW_UG_WIN
-#define FW_UG_WIN 2
+#ifndef FW_MAXR_WIN  // ... of the config-C kernel (profiles/r04_kept_rows_ab.txt, profiles/r06_kept_rows_long.txt)
+#define FW_MAXR_WIN 20
 #endif
-#ifndef FW_UA_WIN
-#define FW_UA_WIN 1
+#ifndef FW_LR_KEEP_MIN  // LR entries an example needs for its update to reuse the pair the forward pass read (profiles/r04_lr_pair_kept_ab.txt)
+#define FW_LR_KEEP_MIN 128
 #endif
-#ifndef FW_WIN_NCH  // 1 KiB chunks per row in the whole-line update.  2 would give the k = 8 rows that span 9 lines their ninth line too: measured slower (3.96 vs 3.86 ms, the extra registers spill)
-#define FW_WIN_NCH 1
-#endif
-#ifndef FW_UO
-#define FW_UO 1
-#endif
-#ifndef FW_LB_THREADS
+#ifndef FW_LB_THREADS  // workgroup size the v2 kernel is compiled for (384 x 5 waves: no scratch and 4-5 % slower, profiles/r02_kernel_resource_usage.txt)
 #define FW_LB_THREADS 512
 #endif
 // 6 waves per SIMD (<= 85 VGPRs): three 512-thread workgroups per CU.  Occupancy beats residency: 2 resident rows per
 // wave at 3 workgroups/CU is 10 % faster (training) / 22 % faster (inference) than 12 resident rows at 2 workgroups/CU.
-#ifndef FW_LB_WAVES
+#ifndef FW_LB_WAVES  // waves per SIMD of the single-chunk instantiations without the window path (profiles/r03_pareto.txt)
 #define FW_LB_WAVES 6
+#endif
+// the window path (config C's updating launches): FOUR waves per SIMD = two workgroups per CU, 128 registers -- room for 14 (round 4: 20) kept rows
+// per wave; faster AND better than three workgroups with 8 kept rows
+#ifndef FW_LB_WAVES_WIN  // waves per SIMD of the config-C kernel (profiles/r03_pareto.txt)
+#define FW_LB_WAVES_WIN 4
+#endif
+#ifndef FW_NN_THREADS  // workgroup size of the instantiation with the deep head as a phase, config E's concurrent launches (profiles/r06_configE_v2_head.txt)
+#define FW_NN_THREADS 512
+#endif
+#ifndef FW_NN_WAVES  // ... and its waves per SIMD (profiles/r06_configE_v2_head.txt)
+#define FW_NN_WAVES 4
 #endif
 // NC = 16-byte chunks per lane and row: 1 for rows of up to 256 floats (config C: 240), 2 for rows of up to 512 floats (k = 16 with 30
 // fields: 480).  Two-chunk rows keep T alone at 57.6 KB of LDS, so two workgroups share a CU and the register budget is 128 VGPRs.
@@ -2774,21 +2786,8 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 // of the table update, every FFM pair and every LR combo slot stepping with its own general gradient.  Two 512-thread workgroups per CU where the generic kernel
 // (which keeps the in-order launches: the parity mode) runs one of 1024 (round 6).
 // PK: the FFM table holds 2-byte buckets (packed_weight above) -- predict-only launches of a packed regressor.  Same lane map as the f32 rows (one lane =
-// four consecutive weights, now ONE 8-byte load), no rows kept for an update that never comes, and FW_UG_PK rows in flight per wave: a row in flight
-// costs two registers instead of four, so the same registers carry the same BYTES in flight at twice the rows.
-#ifndef FW_UG_PK
-#define FW_UG_PK 8
-#endif
+// four consecutive weights, now ONE 8-byte load), no rows kept for an update that never comes, and FW_UG_PK rows in flight per wave.
 template <int OPT, bool COH, int MAXR, bool WIN, int NC = 1, int POL = FW_DEFAULT_STORE_POLICY, bool NN = false, bool PK = false>
-#ifndef FW_LB_WAVES_WIN  // the window path (config C's updating launches): FOUR waves per SIMD = two workgroups per CU, 128 registers -- room for
-#define FW_LB_WAVES_WIN 4  // 14 (round 4: 20) kept rows per wave; faster AND better than three workgroups with 8 kept rows
-#endif
-#ifndef FW_NN_THREADS  // workgroup size / waves per SIMD of the instantiation with the deep head as a phase (config E's concurrent launches)
-#define FW_NN_THREADS 512
-#endif
-#ifndef FW_NN_WAVES
-#define FW_NN_WAVES 4
-#endif
 __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? (WIN ? FW_LB_WAVES_WIN : FW_LB_WAVES) : (NN ? FW_NN_WAVES : 4)) fw_example_kernel_r(const KernelParams /* read through kp_fresh() */) {
     const KernelParams &p = kp_fresh();
     static_assert(NC == 1 || MAXR == 0, "resident rows are a single-chunk feature");
@@ -2797,33 +2796,16 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
     typedef f4 V;
     constexpr int VEC = 4;
     constexpr int AUX = COH ? kAuxSc1 : kAuxPlain;
-// cache-policy bits of the write-back stores: 2 = nt, the L2's streaming replacement policy (still write-back: a hint about WHICH line leaves first).
-// The weight rows take it: a row an example has just written is not read again by that XCD before it is evicted anyway; measured on the 20-kept-rows
-// kernel (profiles/r04_w_nt_and_policy2_on_20_kept_rows.txt): 5.58-5.61 M examples/s against 5.48-5.52 M, hold-out after 10 M examples 0.6233 / 0.6237
-// against 0.6226 / 0.6248.  (On the accumulators of policy 2 it changes neither their dirty lifetime nor the loss: profiles/r04c_policy_ab_nt.txt.)
-#ifndef FW_WB_AUX_W
-#define FW_WB_AUX_W 2
-#endif
-#ifndef FW_WB_AUX_A
-#define FW_WB_AUX_A 0
-#endif
-    // (nt on the device-scope LOADS was measured and rejected: gather -2 %, accumulator loads -4 %, profiles/r04_nt_loads_and_flush256_ab.txt)
+    // The write-back stores of the weight rows are nt (kAuxNt): a row an example has just written is not read again by that XCD before it is evicted
+    // anyway (profiles/r04_w_nt_and_policy2_on_20_kept_rows.txt).  Policy 2's write-back accumulator stores stay plain, and so do all loads.
     constexpr int AUX_G = AUX, AUX_LA = AUX;
-    constexpr int AUX_SW = (COH && POL < 1) ? kAuxSc1 : (COH ? FW_WB_AUX_W : kAuxPlain);  // weight-row stores (store policy: top of this file; 3 = 1 here)
-    constexpr int AUX_SA = (COH && (POL < 2 || POL >= 3)) ? kAuxSc1 : (COH ? FW_WB_AUX_A : kAuxPlain);  // accumulator-row stores
+    constexpr int AUX_SW = (COH && POL < 1) ? kAuxSc1 : (COH ? kAuxNt : kAuxPlain);  // weight-row stores (store policy: top of this file; 3 = 1 here)
+    constexpr int AUX_SA = (COH && (POL < 2 || POL >= 3)) ? kAuxSc1 : kAuxPlain;  // accumulator-row stores
     constexpr bool kThin = COH && POL >= 3;  // thinned accumulator traffic on hot rows (store policies 3 and 4)
     constexpr bool kAtom = COH && POL == 4;  // ... as atomic adds of m g^2 (policy 4) instead of stores of acc_read + m g^2 (policy 3)
     constexpr int UA = (WIN && NC == 1) ? FW_UA_WIN : FW_UA;  // accumulator rows in flight per wave in the update phase
     constexpr int UG = PK ? FW_UG_PK : ((WIN && NC == 1) ? FW_UG_WIN : FW_UG);  // overflow rows in flight per wave in the gather
-#ifndef FW_UO_NN
-#define FW_UO_NN FW_UO
-#endif
-#ifndef FW_UO_NC2  // ... of the headless two-chunk instantiations
-#define FW_UO_NC2 FW_UO
-#endif
-    // overflow rows (w + acc) in flight per wave.  (With the deep head, FW_UO_NN: 2, 4 and 5 rows per round trip were measured against 1 in round 6 -- 1.31-1.34 / 1.26 / 1.28-1.30 M
-    // examples/s against 1.33-1.39 M: the update's share of an example's lifetime does not shrink with the rows in flight, profiles/r06_configE_v2_head.txt.)
-    constexpr int UO = NN ? FW_UO_NN : (NC == 2 ? FW_UO_NC2 : FW_UO);
+    constexpr int UO = FW_UO;  // overflow rows (w + acc) in flight per wave in the update (2 / 4 / 5 were measured with the head: no gain, profiles/r06_configE_v2_head.txt)
     extern __shared__ __align__(16) unsigned char smem[];
     // Single-chunk rows (configs B / C): the AdaGrad LUT is ALWAYS the LDS copy, decided at compile time -- s.lut is then an LDS pointer the
     // compiler can see through (ds_read_b32).  As a run-time choice between the LDS copy and the global table the pointer was generic: every
@@ -2968,39 +2950,22 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         if (cnt == 0) lo = 0;
 
         // ---------------- gather: all row loads up front, rows stay resident
-        // Which rows of the range are kept: the first MAXR -- or (-DFW_KEEP_LAST=1, config-C kernel) the LAST MAXR: the overflow rows then come FIRST in
-        // buffer order and are gathered first, eight at a time, in the registers the kept rows do not occupy yet -- one round trip for them instead of
-        // one per pair behind the kept rows'.  Measured (profiles/r04_keep_last_ab.txt): +1.2 % examples/s (0.576 against 0.569 of the peak) and a
-        // hold-out loss 0.004-0.005 HIGHER from 4 M examples on (0.6297-0.6345 against 0.6244-0.6293 after 10 M, three runs each): the kept rows are
-        // then gathered ~10 us later, their w_gather - step overwrites less of what concurrent examples did, and that damping is what the loss rests
-        // on.  Not the default.  The field sums are accumulated in buffer order either way.
-#ifndef FW_KEEP_LAST
-#define FW_KEEP_LAST 0
-#endif
-#ifndef FW_UG_FIRST
-#define FW_UG_FIRST 8
-#endif
-        constexpr bool kKeepLast = FW_KEEP_LAST && FW_PIPE_UPD && WIN && NC == 1 && MAXR > 0;
+        // The FIRST MAXR rows of the range are kept, gathered as early as can be: their w_gather - step overwrites what concurrent examples did to them
+        // meanwhile, and that damping is what the hold-out loss rests on (keeping the last MAXR instead: profiles/r04_keep_last_ab.txt).
         const uint32_t nk = cnt < (uint32_t)MAXR ? cnt : (uint32_t)MAXR;  // rows kept
-        constexpr bool kLdsKeep = FW_LDS_KEEP_MAX > 0 && !kKeepLast && FW_PIPE_UPD && WIN && NC == 1 && MAXR > 0;
+        constexpr bool kLdsKeep = WIN && NC == 1 && MAXR > 0;
         constexpr int LKM = kLdsKeep ? FW_LDS_KEEP_MAX : 0;
         const uint32_t lk = kLdsKeep ? p.lds_keep : 0u;                                          // rows of this launch kept in LDS per wave
         const uint32_t nk2 = cnt < (uint32_t)MAXR + lk ? cnt : (uint32_t)MAXR + lk;              // rows kept, registers + LDS
-        const uint32_t kb = kKeepLast ? hi - nk : lo;                      // the first of them (cnt == 0: lo == hi == 0)
         V rows[MAXR > 0 ? MAXR : 1];
         // packed rows: the file header's two words, launch constants (launch_packed_predict hands them over in the FFM block's two optimizer
         // parameters, which a predict-only launch never reads: the argument block keeps its size and every field its place)
         const float pk_inc = PK ? p.ffm_rate : 0.0f, pk_min = PK ? p.ffm_minus_power_t : 0.0f;
         // The rows parked in LDS go there DIRECTLY (LDS-direct loads: no register in between), issued in the same burst as the register rows' loads instead
-        // of two at a time behind them: destination = wave-uniform slot base + lane * 16.  -DFW_PARK_FIRST=1 issues them in FRONT of the register rows' loads.
-#ifndef FW_PARK_ASM
-#define FW_PARK_ASM 1  // (default since round 6: +0.5-1.2 % in three of three interleaved pairs, profiles/r06_park_asm_ab.txt; 0 = the compiler-issued LDS-direct loads)
-#endif
-#ifndef FW_PARK_FIRST
-#define FW_PARK_FIRST FW_PARK_ASM
-#endif
+        // of two at a time behind them: destination = wave-uniform slot base + lane * 16.  The asm form issues them in FRONT of the register rows' loads.
+        constexpr bool kParkFirst = FW_PARK_ASM;
         auto park_rows = [&]() {
-            if (kLdsKeep && FW_PARK_DIRECT) {
+            if (kLdsKeep) {
 #pragma unroll
                 for (int j = 0; j < LKM; ++j) {
                     if ((uint32_t)(MAXR + j) < nk2) {
@@ -3030,18 +2995,16 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                 }
             }
         };
-        if (!kKeepLast) {
-            if (FW_PARK_FIRST) park_rows();
+        if (kParkFirst) park_rows();
 #pragma unroll
-            for (int sl = 0; sl < MAXR; ++sl) {
-                // (a slot beyond the range loads through a zero-length descriptor: zeros, no memory access -- as a branch around the load every
-                // slot's `sl < nk` became a lane mask that lived from here to the end of the burst, 40 scalar registers for 20 rows)
-                const bool on = (uint32_t)sl < nk;
-                const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[kb + sl]);  // (beyond the range: some word of the LDS, unused)
-                rows[sl] = Vec<VEC>::template load<AUX_G>(make_rsrc(p.ffm_w + h, on ? R * 4 : 0u), e0 * 4);
-            }
-            if (!FW_PARK_FIRST) park_rows();
+        for (int sl = 0; sl < MAXR; ++sl) {
+            // (a slot beyond the range loads through a zero-length descriptor: zeros, no memory access -- as a branch around the load every
+            // slot's `sl < nk` became a lane mask that lived from here to the end of the burst, 40 scalar registers for 20 rows)
+            const bool on = (uint32_t)sl < nk;
+            const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[lo + sl]);  // (beyond the range: some word of the LDS, unused)
+            rows[sl] = Vec<VEC>::template load<AUX_G>(make_rsrc(p.ffm_w + h, on ? R * 4 : 0u), e0 * 4);
         }
+        if (!kParkFirst) park_rows();
         {
             V acc[NC];
 #pragma unroll
@@ -3082,32 +3045,6 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             }                                                                                                 \
         }                                                                                                     \
     }
-            if (kKeepLast) {
-                // overflow rows [lo, kb) first: transient (they are re-read in the update phase)
-                constexpr int UGF = FW_UG_FIRST;
-                for (uint32_t i = lo; i < kb; i += UGF) {
-                    V r[UGF][NC];
-#pragma unroll
-                    for (int u = 0; u < UGF; ++u) {
-                        r[u][0] = Vec<VEC>::zero();
-                        if (i + u < kb) {
-                            const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[i + u]);
-                            r[u][0] = Vec<VEC>::template load<AUX_G>(make_rsrc(p.ffm_w + h, R * 4), e0 * 4);
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < UGF; ++u)
-                        if (i + u < kb) FW_CONSUME(r[u], i + u)
-                }
-#pragma unroll
-                for (int sl = 0; sl < MAXR; ++sl) {
-                    rows[sl] = Vec<VEC>::zero();
-                    if ((uint32_t)sl < nk) {
-                        const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[kb + sl]);
-                        rows[sl] = Vec<VEC>::template load<AUX_G>(make_rsrc(p.ffm_w + h, R * 4), e0 * 4);
-                    }
-                }
-            }
             // (the count is handed out afresh: compared with the SAME value as in the burst above, every slot's `sl < nk` is computed once, up there,
             // and kept as a 64-bit lane mask until its row is consumed -- two scalar registers per kept row)
             uint32_t nk_c = __builtin_amdgcn_readfirstlane(nk);
@@ -3117,9 +3054,9 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                 if ((uint32_t)sl < nk_c) {
                     V one[NC];
                     one[0] = rows[sl];
-                    FW_CONSUME(one, kb + sl)
+                    FW_CONSUME(one, lo + sl)
                 }
-            if (kLdsKeep && FW_PARK_DIRECT) {
+            if (kLdsKeep) {
                 // rows parked in LDS: their loads were issued right behind the register rows', which have all been consumed by now (vmcnt counts in
                 // order: nothing else of this wave is in flight)
                 if (nk2 > (uint32_t)MAXR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3133,7 +3070,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                     }
             }
             // overflow rows of this range: transient (they are re-read in the update phase)
-            for (uint32_t i = kKeepLast ? hi : ((kLdsKeep && FW_PARK_DIRECT) ? lo + nk2 + (nk2 < (uint32_t)MAXR ? (uint32_t)MAXR - nk2 : 0u) : lo + MAXR); i < hi; i += UG) {
+            for (uint32_t i = kLdsKeep ? lo + nk2 + (nk2 < (uint32_t)MAXR ? (uint32_t)MAXR - nk2 : 0u) : lo + MAXR; i < hi; i += UG) {
                 V r[UG][NC];
                 u2 raw[PK ? UG : 1][NC];  // packed rows: the buckets as loaded; converted where the row is consumed
 #pragma unroll
@@ -3159,9 +3096,6 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                             for (int c = 0; c < NC; ++c) r[u][c] = packed_weights4(raw[PK ? u : 0][c], pk_inc, pk_min);
                         }
                         FW_CONSUME(r[u], i + u)
-                        // the first lds_keep of them stay in LDS for the update phase (as read HERE, like a register-kept row)
-                        if (kLdsKeep && !FW_PARK_DIRECT && inb && i + u - (lo + MAXR) < lk)
-                            Vec<VEC>::lds_store(s.keep + ((uint32_t)wave * lk + (i + u - (lo + MAXR))) * R + e0, r[u][0]);
                     }
             }
             if (cur != 0xffffffffu) {
@@ -3338,9 +3272,6 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             // The pair kept from the forward pass saves the update's load round trip: +1.8 % examples/s at config C at the same loss.  Only for
             // examples of at least FW_LR_KEEP_MIN LR entries: on streams of small examples (10-40 entries, ~15 us per example) the longer
             // read-modify-write window of the hot LR entries costs 0.005-0.01 of hold-out loss (profiles/r04_lr_pair_kept_ab.txt; round 2 saw the same).
-#ifndef FW_LR_KEEP_MIN
-#define FW_LR_KEEP_MIN 128
-#endif
             if (lr_upd) lr_update<OPT, COH>(p, s, nl, g, gx, lut_lr, tid, bd, 0u, 0xffffffffu, !NN && nl >= FW_LR_KEEP_MIN, lr_kept,
                                             (WIN && (kAtom || NC == 2) && p.store_policy == 4 && p.lr_thin && p.grid_wgs > 1) ? ex : 0xffffffffu);  // (the large-table path only)
             FW_TICK(4);
@@ -3348,13 +3279,13 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             // Chained duplicates (WIN): a row that is chained to an earlier one is applied by that row's owner, and an owner WITH a
             // chain applies it from the window path below (which walks the chain): neither is stepped here.
             constexpr uint32_t kResSkip = WIN ? (kRowDep | kRowChained | kRowHasChain) : kRowDep;
-            if (FW_PIPE_UPD && WIN && NC == 1 && MAXR > 0) {
+            if (WIN && NC == 1 && MAXR > 0) {
                 // Every kept slot goes through the same instructions; a slot without a row (beyond the wave's range, or a row the window path
                 // applies) gets descriptors of zero length: its loads return 0, its stores are dropped.  With no branch between them the compiler
                 // counts the memory operations exactly (s_waitcnt vmcnt(n) instead of vmcnt(0)): waiting for row sl + 1's accumulators does not
                 // wait for the acknowledgement of row sl's stores any more.
-                // (the range's first index is handed out afresh: as the gather's own `kb`, every slot's kb + sl stayed in a scalar register from the gather to here)
-                uint32_t kb_u = __builtin_amdgcn_readfirstlane(kb);
+                // (the range's first index is handed out afresh: as the gather's own `lo`, every slot's lo + sl stayed in a scalar register from the gather to here)
+                uint32_t kb_u = __builtin_amdgcn_readfirstlane(lo);
                 // (... and so is the per-wave count of rows parked in LDS: with the gather's own `lk` this lane's address in the parked rows' slots is computed
                 // once, up there, and kept in a vector register through the dot phase -- spilled in this 128-register kernel, and its reload from scratch HERE
                 // is an s_waitcnt vmcnt(0): every parked row's step then waited for the acknowledgement of every store of the rows before it)
@@ -3393,7 +3324,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                     V a_cur = av[sl];
                     // store policy 3: is this a hot row (wave-uniform: any lane's accumulator beyond theta), and is this example the one in m that stores it?
                     float g2_scale = 0.0f;
-                    bool acc_store = ok0, acc_add = false, hot_row = false;
+                    bool acc_store = ok0, acc_add = false;
                     if (kThin && (kAtom || sl < MAXR) && p.grid_wgs > 1) {  // (policy 3: rows kept in registers only: a thinned STORE on a row parked in LDS -- stepped last, behind the longest window -- loses its race more often, tests/test_gpu_conservation.py; an atomic add has no race to lose)
                         const bool hot = __ballot(a_cur[0] > p.acc_hot_theta || a_cur[1] > p.acc_hot_theta || a_cur[2] > p.acc_hot_theta || a_cur[3] > p.acc_hot_theta) != 0ull;
                         if (hot) {
@@ -3402,8 +3333,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                             const bool turn = ok0 && (draw & (m - 1u)) == 0u;
                             acc_store = kAtom ? false : turn;
                             acc_add = kAtom && turn;
-                            g2_scale = kAtom ? (float)m : (float)(m - 1u);
-                            hot_row = true;
+                            g2_scale = (float)(m - 1u);
                         }
                     }
                     const float v = s.e_val[kb_u + (uint32_t)sl];
@@ -3425,24 +3355,15 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                         const float grad = __fmul_rn(g, G);
                         float acc = a_cur[j];
                         const float upd = opt_step<OPT>(grad, acc, p.ffm_rate, p.ffm_minus_power_t, s.lut);
-                        // (what is STORED for a thinned row: m x this example's g^2 on top of what it read; policy 4, strided form: what is ADDED to a hot row, m x this example's g^2)
-                        a_cur[j] = kAtom ? ((!FW_ATOM_COALESCED && hot_row) ? g2_scale * (grad * grad) : acc) : (kThin ? acc + g2_scale * (grad * grad) : acc);
+                        // (what is STORED for a thinned row of policy 3: m x this example's g^2 on top of what it read; policy 4 ADDS its share behind the loop)
+                        a_cur[j] = (kThin && !kAtom) ? acc + g2_scale * (grad * grad) : acc;
                         wv[j] = wv[j] - upd;  // block_ffm.rs:282
                     }
                     Vec<VEC>::template store<AUX_SW>(wv, make_rsrc(p.ffm_w + h0, ok0 ? R * 4 : 0), e0 * 4);
                     if (OPT != FWGPU_OPT_SGD) Vec<VEC>::template store<AUX_SA>(a_cur, make_rsrc(p.ffm_acc + h0, (kThin ? acc_store : ok0) ? R * 4 : 0), e0 * 4);
-                    if (kAtom && OPT != FWGPU_OPT_SGD) {
-#if FW_ATOM_COALESCED
-                        add_mask |= (acc_add ? 1u : 0u) << sl;  // (the adds themselves: behind the loop, where no row is alive in registers any more)
-#else
-                        // fire-and-forget (no return value: nothing waits for them); a row that is not hot, or not this example's turn, adds through a zero-length descriptor: dropped
-                        const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.ffm_acc + h0, acc_add ? R * 4 : 0);
-#pragma unroll
-                        for (int j = 0; j < VEC; ++j) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(a_cur[j], ra, (int)(e0 * 4 + 4 * j), 0, kAuxSc1);
-#endif
-                    }
+                    if (kAtom && OPT != FWGPU_OPT_SGD) add_mask |= (acc_add ? 1u : 0u) << sl;  // (the adds themselves: behind the loop, where no row is alive in registers any more)
                 }
-                if (kAtom && FW_ATOM_COALESCED && OPT != FWGPU_OPT_SGD) {
+                if (kAtom && OPT != FWGPU_OPT_SGD) {
                     // Store policy 4's adds: fire-and-forget (no return value: nothing waits for them) and COALESCED -- lane l adds to floats l, 64 + l, 128 + l,
                     // 192 + l of the row, so one instruction covers 256 contiguous bytes = four 64-byte requests of 16 floats each (in the step's own layout, 4
                     // consecutive floats per lane, an instruction touches sixteen 64-byte segments with 4 floats each: four times the requests at the memory
@@ -3480,7 +3401,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                     for (int u = 0; u < UA; ++u) {
                         av[u] = Vec<VEC>::zero();
                         if (OPT != FWGPU_OPT_SGD && (uint32_t)(g0 + u) < nk) {
-                            const uint32_t i = kb + g0 + u;
+                            const uint32_t i = lo + g0 + u;
                             if (!(s.e_fld[i] & kResSkip)) {
                                 const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[i]);
                                 av[u] = Vec<VEC>::template load<AUX_LA>(make_rsrc(p.ffm_acc + h, R * 4), e0 * 4);
@@ -3490,7 +3411,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
 #pragma unroll
                     for (int u = 0; u < UA; ++u) {
                         if (g0 + u < MAXR && (uint32_t)(g0 + u) < nk) {
-                            const uint32_t i = kb + g0 + u;
+                            const uint32_t i = lo + g0 + u;
                             const uint32_t fb = s.e_fld[i];
                             if (!(fb & kResSkip)) {
                                 const uint32_t f = __builtin_amdgcn_readfirstlane(fb & kFldMask);
@@ -3527,10 +3448,10 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                     const uint32_t i = i0 + u;
                     idx[u] = (i < hi && !(s.e_fld[i] & (kRowDep | kRowChained))) ? i : 0xffffffffu;
                     // (the first MAXR rows of the range were stepped from registers, unless they own a chain)
-                    if (WIN && MAXR > 0 && i >= kb && i < kb + nk2 && !(s.e_fld[i] & kRowHasChain)) idx[u] = 0xffffffffu;
+                    if (WIN && MAXR > 0 && i >= lo && i < lo + nk2 && !(s.e_fld[i] & kRowHasChain)) idx[u] = 0xffffffffu;
                 }
                 if (WIN)
-                    update_rows_win<OPT, AUX, UO, (NC > FW_WIN_NCH ? NC : FW_WIN_NCH), AUX_SW, AUX_SA>(p, s, idx, g, lane, nf, gpair, (kThin && (NC > 1 || kAtom) && p.store_policy >= 3 && p.grid_wgs > 1 && p.thin_reread) ? ex : 0xffffffffu);
+                    update_rows_win<OPT, AUX, UO, NC, AUX_SW, AUX_SA>(p, s, idx, g, lane, nf, gpair, (kThin && (NC > 1 || kAtom) && p.store_policy >= 3 && p.grid_wgs > 1 && p.thin_reread) ? ex : 0xffffffffu);
                 else
                     update_rows<VEC, OPT, AUX, UO, false, NC>(p, s, idx, g, lane);
             }
@@ -3543,7 +3464,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                         if (s.e_fld[i] & kRowDep) {
                             uint32_t idx[1] = {i};
                             if (WIN)
-                                update_rows_win<OPT, AUX, 1, (NC > FW_WIN_NCH ? NC : FW_WIN_NCH), AUX_SW, AUX_SA>(p, s, idx, g, lane, nf, gpair);
+                                update_rows_win<OPT, AUX, 1, NC, AUX_SW, AUX_SA>(p, s, idx, g, lane, nf, gpair);
                             else
                                 update_rows<VEC, OPT, AUX, 1, false, NC>(p, s, idx, g, lane);
                             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -3586,12 +3507,6 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
 #undef FW_TID_FRESH
 }
 
-#ifndef FW_MAXR
-#define FW_MAXR 2
-#endif
-#ifndef FW_MAXR_WIN
-#define FW_MAXR_WIN 20
-#endif
 #ifndef FW_PHASE_TU  // (the fused kernels' launchers and the small utility kernels: first translation unit only)
 template <int OPT, bool COH>
 static hipError_t launch_r(const KernelParams &p, uint32_t grid, uint32_t threads, size_t lds, hipStream_t stream) {
@@ -3657,7 +3572,7 @@ void resolve_row_mode(KernelParams &p, uint32_t threads) {
     // (two-chunk rows only: config C's kernel has the LDS to spare, and the choice costs its update two vector registers it does not have)
     p.no_selfw = (uses_resident_kernel(p, threads) && (!p.update || (p.window && p.concurrent && p.R > 64 * 4 && !selfw_lds_forced))) ? 1 : 0;
     // rows kept in LDS beyond the register-kept ones: the chained-update instantiation of single-chunk rows only (fw_example_kernel_r, FW_LDS_KEEP_MAX)
-    if (!(p.lut_lds_forced && p.window) || FW_KEEP_LAST || p.no_kept_rows) p.lds_keep = 0;
+    if (!(p.lut_lds_forced && p.window) || p.no_kept_rows) p.lds_keep = 0;
     if (p.lds_keep > FW_LDS_KEEP_MAX) p.lds_keep = FW_LDS_KEEP_MAX;
     p.lds_keep_words = p.lds_keep * (threads / 64) * p.R;
 }

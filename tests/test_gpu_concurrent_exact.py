@@ -6,7 +6,7 @@ this kind of stream, by the anchors below.  helpers.disjoint_stream builds such 
 translator's output; the models have no constant feature (its LR entry is the one thing every example would share).
 
 What would turn which case red (the code paths exist only when p.concurrent / p.grid_wgs > 1, or at launch shapes an in-order launch never takes):
-  * a coalesced add (store policy 4, FW_ATOM_COALESCED) shifted by one float: the gradients differ per float here, so every hot kept row of
+  * a coalesced add (store policy 4: the adds behind the pipelined update loop) shifted by one float: the gradients differ per float here, so every hot kept row of
     test_hot_rows_one_example_in_one is off by far more than its one ulp per occurrence;
   * the second chunk's add dropped: the floats from 256 on of the hot rows of test_hot_rows_one_example_in_one[c_k16 / c_f40] keep their preset
     value where the in-order launch grew them; under the default sampling the unit shows 0 where its share of turns must be 1/8;
