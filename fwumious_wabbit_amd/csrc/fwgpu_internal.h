@@ -191,11 +191,13 @@ struct KernelParams {
     // ---- serving context cache (regressor.rs:397-423, block_ffm.rs:442-782): the context features' field sums, in T's layout
     const float *ctx_T;                 // [F*R] T[z][f][k] partial sums of the cached features (NULL: none); read-only launches only
     const float *ctx_dcf;               // [F]   their self-pair corrections
+    const uint32_t *ctx_cnt;            // [F]   how many cached features each field has (the head's input diagonal: a field of ONE feature, cached or gathered, gives exactly 0)
     const uint32_t *ctx_rec;            // candidate-only record batches: the context's record (namespaces a candidate's record lacks come from it)
     uint32_t ctx_rec_len;
     const uint32_t *ctx_cover;          // record batches: bit per namespace slot whose FFM features the cache already holds (the stage phase skips them)
-    float *emit_T;                      // setup_cache: example 0's T and dcf are written here after the gather
+    float *emit_T;                      // setup_cache: example 0's T, dcf and per-field feature counts are written here after the gather
     float *emit_dcf;
+    uint32_t *emit_cnt;
 #if defined(FW_KP_PAD_POS) && FW_KP_PAD_POS == 1  // debug builds (scripts/kp_pos_exp.sh): 16 bytes HERE
     unsigned char kp_pos_pad[16];
 #endif
@@ -335,6 +337,7 @@ struct fwgpu_batch {
     fwgpu_regressor *owner = nullptr;
     const fwgpu_block_cache *cache = nullptr;  // context cache the next predict-only launch of this batch starts from
     float *emit_T = nullptr, *emit_dcf = nullptr;  // setup_cache launch: where example 0's field sums go
+    uint32_t *emit_cnt = nullptr;                  // ... and its features per field
     uint32_t n = 0;
     uint64_t n_lr = 0, n_ffm = 0;
     uint32_t max_lr = 0, max_ffm = 0;
@@ -425,8 +428,9 @@ struct fwgpu_split {
 // Vec<BlockCache> of the reference (regressor.rs:40-50): what setup_cache leaves behind for predict_with_cache
 struct fwgpu_block_cache {
     fwgpu_regressor *owner = nullptr;
-    float *d_T = nullptr;    // [F*R] + [F] (dcf) in one allocation
+    float *d_T = nullptr;    // [F*R] + [F] (dcf) + [F] (cnt) in one allocation
     float *d_dcf = nullptr;
+    uint32_t *d_cnt = nullptr;  // cached features per field, as the setup launch counted them (a repeated feature counts twice, as in the field sums)
     std::vector<uint64_t> present;  // sorted (hash << 32 | contra_field_index) of the cached FFM features (features_present)
     // record batches (fwgpu_block_cache_cover_record): the context's record decides which namespace slots are covered
     uint32_t *d_cover = nullptr;           // device copy of `cover`, followed by the context's record

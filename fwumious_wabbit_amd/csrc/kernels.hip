@@ -914,6 +914,12 @@ __device__ __forceinline__ float nn_forward(const KernelParams &p, const Lds &s,
         float dot = 0.0f;
         if (i != j) {
             for (uint32_t kk = 0; kk < k; ++kk) dot += s.T[i * R + j * k + kk] * s.T[j * R + i * k + kk];
+        } else if (!COH && p.ctx_cnt && p.ctx_cnt[i]) {
+            // (read-only launch with a context cache that holds features of this field: T and dcf carry their share, the entries in LDS do not.  One rule for
+            // cached + gathered features together: exactly 0 for a field of one feature, 0.5 (|field sum|^2 - sum of the features' own squares) otherwise --
+            // the form split_mid_kernel and the batched predict-only head use.  A field the cache holds nothing of keeps the forms below, bit for bit.)
+            for (uint32_t kk = 0; kk < k; ++kk) dot += s.T[i * R + i * k + kk] * s.T[i * R + i * k + kk];
+            dot = (p.ctx_cnt[i] + (s.fend[i] - s.fstart[i])) <= 1u ? 0.0f : 0.5f * (dot - s.dcf[i]);
         } else if (p.no_selfw) {
             // (launches that keep no LDS copy of the entries' own slots -- the v2 kernel's concurrent two-chunk launches: the diagonal as split_mid_kernel and
             // the batched predict-only head form it: exactly 0 for a field of at most one feature, 0.5 (|field sum|^2 - sum of the features' own squares) otherwise)
@@ -1990,7 +1996,10 @@ __global__ void __launch_bounds__(1024) fw_example_kernel(const KernelParams /* 
         FW_TICK(2);
         if (kCtx && p.emit_T && ex == 0) {  // setup_cache: keep this example's field sums (Regressor::setup_cache, regressor.rs:409-423)
             for (uint32_t i = tid; i < F * R; i += bd) p.emit_T[i] = s.T[i];
-            for (uint32_t f = tid; f < F; f += bd) p.emit_dcf[f] = s.dcf[f];
+            for (uint32_t f = tid; f < F; f += bd) {
+                p.emit_dcf[f] = s.dcf[f];
+                p.emit_cnt[f] = s.fend[f] - s.fstart[f];  // (the head's input diagonal needs to know a field of one feature from a field of several: nn_forward)
+            }
         }
         if (PH == 1) {
             // ---------------- FWD: this rank's share of the example goes to its split record
@@ -3134,7 +3143,10 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         }
         if (!COH && p.emit_T && ex == 0) {  // setup_cache: keep this example's field sums (Regressor::setup_cache, regressor.rs:409-423)
             for (uint32_t i = tid; i < F * R; i += bd) p.emit_T[i] = s.T[i];
-            for (uint32_t f = tid; f < F; f += bd) p.emit_dcf[f] = s.dcf[f];
+            for (uint32_t f = tid; f < F; f += bd) {
+                p.emit_dcf[f] = s.dcf[f];
+                p.emit_cnt[f] = s.fend[f] - s.fstart[f];  // (as in fw_example_kernel)
+            }
         }
 
         float wsum_nn = 0.0f;
@@ -3215,7 +3227,8 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                 for (uint32_t kk = 0; kk < k; ++kk) d += s.T[i * R + j * k + kk] * s.T[j * R + i * k + kk];
                 // the diagonal as split_mid_kernel forms it: exactly 0 for a field of at most one feature, 0.5 (|field sum|^2 - sum of the features' own squares) otherwise
                 // (the per-feature form of the training forward needs the entries' own slots in LDS, which a read-only launch does not keep)
-                if (i == j) d = (s.fend[i] - s.fstart[i]) <= 1u ? 0.0f : 0.5f * (d - s.dcf[i]);
+                // (with a context cache the field's features are the cached ones -- whose share T and dcf already carry -- and the gathered ones together)
+                if (i == j) d = ((p.ctx_cnt ? p.ctx_cnt[i] : 0u) + (s.fend[i] - s.fstart[i])) <= 1u ? 0.0f : 0.5f * (d - s.dcf[i]);
                 x[C + t] = d;
             }
             if (tid == 0) {

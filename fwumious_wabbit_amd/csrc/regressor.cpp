@@ -384,6 +384,7 @@ KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int upd
     if (!update && b->cache) {  // predict_with_cache: the field sums start from the cached features' (regressor.rs:397-407)
         p.ctx_T = b->cache->d_T;
         p.ctx_dcf = b->cache->d_dcf;
+        p.ctx_cnt = b->cache->d_cnt;
         if (b->records) p.ctx_cover = b->cache->d_cover;
         if (b->records && b->delta_records) {
             p.ctx_rec = b->cache->d_ctx_rec;
@@ -393,6 +394,7 @@ KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int upd
     if (!update) {
         p.emit_T = b->emit_T;
         p.emit_dcf = b->emit_dcf;
+        p.emit_cnt = b->emit_cnt;
     }
     p.records = b->records;
     p.rec_self_len = b->rec_self_len ? 1 : 0;
@@ -591,7 +593,7 @@ static constexpr uint32_t kHeadPredictSlab = 32768;
 static bool head_predict_batched(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update) {
     static const bool env_off = getenv("FWGPU_HEAD_PREDICT_PER_EXAMPLE") != nullptr;  // A/B runs: the per-example forward for every launch
     const bool off = r->launch.head_predict >= 0 ? r->launch.head_predict == 0 : env_off;  // (fwgpu_debug_set_option 14 overrides the environment)
-    if (off || update || !r->nn.n_layers || mode != FWGPU_MODE_HOGWILD || b->n < 256 || b->cache || b->emit_T) return false;
+    if (off || update || !r->nn.n_layers || mode != FWGPU_MODE_HOGWILD || b->n < 256 || b->emit_T) return false;
     const uint32_t k = r->cfg.ffm_k, R = k * r->cfg.ffm_num_fields;
     return k && k % 4 == 0 && b->aligned4 && (R <= 256 || (R <= 512 && 256 % k == 0)) && r->launch.kernel_version != 1;
 }
@@ -612,7 +614,10 @@ static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_
     KernelParams p;
     uint32_t threads = 0;
     {   // (prepare_launch with the head's per-example LDS taken out of the picture)
-        p = make_params(r, b, 0);
+        p = make_params(r, b, 0);  // (with the batch's context cache, if it has one: ctx_*)
+        // candidate-only records: the stage phase puts the context's record behind the candidate's in LDS, so the batch's longest record counts both
+        // (serving.cpp sizes max_rec that way; a batch that does not cannot be staged)
+        if (p.ctx_rec && b->max_rec < p.ctx_rec_len) return fail(FWGPU_ERR_RANGE, "candidate-only records: the batch's longest record does not include the context's");
         p.emit_x = 1;
         p.xbuf = r->pred_x;
         p.gbuf = r->pred_yi;
@@ -1498,7 +1503,6 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
                       uint32_t n_ffm, fwgpu_block_cache **cache) {
     if (!r || !cache) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if ((n_lr && !lr) || (n_ffm && !ffm)) return fail(FWGPU_ERR_INVALID, "NULL entry buffer");
-    if (r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "the context cache does not cover models with a deep head");
     if (int rcp = refuse_packed(r, "setup_cache (a device-side context cache)")) return rcp;
     FWGPU_HIP(hipSetDevice(r->device));
     const uint32_t F = r->cfg.ffm_k ? r->cfg.ffm_num_fields : 0, R = F * r->cfg.ffm_k;
@@ -1507,11 +1511,12 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
     if (!c) {  // should_create (regressor.rs:415-417)
         c = new fwgpu_block_cache();
         c->owner = r;
-        if (hipMalloc((void **)&c->d_T, ((size_t)F * R + F + 4) * sizeof(float)) != hipSuccess) {
+        if (hipMalloc((void **)&c->d_T, ((size_t)F * R + 2 * (size_t)F + 4) * sizeof(float)) != hipSuccess) {
             delete c;
             return fail(FWGPU_ERR_DEVICE, "setup_cache: allocation failed");
         }
         c->d_dcf = c->d_T + (size_t)F * R;
+        c->d_cnt = reinterpret_cast<uint32_t *>(c->d_dcf + F);  // (features per field: what the deep head's input diagonal asks, nn_forward)
     }
     HostBatch hb;
     hb.clear();
@@ -1523,8 +1528,10 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
         r->one->cache = nullptr;
         r->one->emit_T = c->d_T;
         r->one->emit_dcf = c->d_dcf;
+        r->one->emit_cnt = c->d_cnt;  // (a refilled cache: T, dcf and the counts are all written again by this launch)
         rc = run_batch(r, r->one, FWGPU_MODE_SEQUENTIAL, 0, 0);
         r->one->emit_T = r->one->emit_dcf = nullptr;
+        r->one->emit_cnt = nullptr;
     }
     if (rc == FWGPU_OK && one_prediction(r, &pred) != FWGPU_OK) rc = fail(FWGPU_ERR_DEVICE, "setup_cache: launch failed");
     if (rc != FWGPU_OK) {

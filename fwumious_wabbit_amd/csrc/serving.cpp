@@ -10,7 +10,10 @@
 // of a request in one launch, as records: the kernel's own translation leaves out the namespaces the cache covers
 // (fwgpu_block_cache_cover_record); a request in which some candidate names a context namespace again, or carries a feature
 // equal to a cached one, takes the entry route (host translation + fwgpu_block_cache_filter), which is the reference's rule
-// for those.  Models with a deep head, and predictors created with --packed_weights, keep the uncached route (whole line scored), which gives the same result.
+// for those.  Models with a deep head are served through the cache like any other (block_neural.rs:355, block_misc.rs:847, block_relu.rs:123: every block
+// behind the FFM block inherits forward_with_cache): the cache also keeps how many features it holds per field, which is what the head's input diagonal
+// needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (regressor.cpp run_batch_head_predict), a smaller one
+// the per-example kernel.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -254,8 +257,8 @@ float fw_setup_cache(FfiPredictor *ptr, const char *input_buffer) {  // lib.rs:2
     ptr->prefix = nullptr;
     if (fwgpu_parse_prefix_create(ptr->parser, ptr->cached_text.data(), ptr->cached_text.size(), &ptr->prefix) != FWGPU_OK) return kExceptionErrorCode;
     SharedModel &m = *ptr->model;
-    // (a packed regressor keeps no device-side context cache: like a model with a deep head, the whole context + candidate record is scored)
-    if (m.re->nn.n_layers == 0 && m.re->cfg.ffm_k != 0 && !m.re->packed()) {
+    // (a packed regressor keeps no device-side context cache: the whole context + candidate record is scored)
+    if (m.re->cfg.ffm_k != 0 && !m.re->packed()) {
         // translate_and_filter(buffer, 0, Some(Primitive)) + Regressor::setup_cache (lib.rs:133-146); every namespace this
         // library accepts is primitive (transformed namespaces are refused when the model is loaded)
         float label, imp;

@@ -125,7 +125,11 @@ int fwgpu_predict(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_lr, c
  * The cache is BlockFFM's (block_ffm.rs:442-782): the context features' field sums and self-pair corrections, computed once
  * on the device, plus `features_present` (regressor.rs:25-38: hash + contra_field_index).  A candidate then gathers only the
  * FFM rows of the features that are not present in the cache.  BlockLR's cache never holds anything in the reference
- * (block_lr.rs:236-239 skips every masked hash), so LR entries are all read, as there.  Models with a deep head: refused.
+ * (block_lr.rs:236-239 skips every masked hash), so LR entries are all read, as there.  Models with a deep head are covered (every
+ * block behind the FFM block inherits forward_with_cache, block_neural.rs:355): the cache also keeps how many features it holds per
+ * field, and the head's input diagonal of a field with c cached and n gathered features is what an uncached launch computes for
+ * c == 0, exactly 0 for c + n <= 1, and 0.5 (|field sum|^2 - sum of the features' own squares) otherwise.  A second
+ * fwgpu_setup_cache on the same handle refreshes sums and counts.  Packed regressors: refused.
  * fwgpu_block_cache_filter: the FFM entries forward_with_cache still gathers (what an entry batch used with
  * fwgpu_batch_set_cache: must hold); predict-only launches of that batch then start every example from the cache. */
 typedef struct fwgpu_block_cache fwgpu_block_cache;
@@ -477,7 +481,8 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value);
 /* Which path the regressor's last fwgpu_learn_batch took (read-only; the single-example calls do not change it): */
 #define FWGPU_ROUTE_NONE 0                 /* no batch launch yet, or an empty batch */
 #define FWGPU_ROUTE_FUSED 1                /* the fused example kernel, the deep head (if any) per example inside it */
-#define FWGPU_ROUTE_HEAD_BATCHED 2         /* predict-only batch of a deep head: head inputs to a batch buffer, layers as GEMMs (option 14) */
+#define FWGPU_ROUTE_HEAD_BATCHED 2         /* predict-only batch of a deep head: head inputs to a batch buffer, layers as GEMMs (option 14); with or without a
+                                            * context cache (fwgpu_batch_set_cache: filtered entries, records with covered slots, candidate-only records) */
 #define FWGPU_ROUTE_HEAD_BATCHED_REFUSED 3 /* ... which refused the batch's shape (FWGPU_ERR_RANGE); the batch was re-run on the fused example kernel, per example */
 #define FWGPU_ROUTE_PACKED 4               /* packed regressor: the packed predict kernel (or its refusal) */
 #define FWGPU_ROUTE_HOST_WALK 5            /* a batch with an oversize example: walked example by example from its host copy */
