@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("FWGPU_LIBRARY") or os.path.join(_HERE, "lib", "libfwg
 
 OK = 0
 ERR_INVALID = 1
+ERR_RANGE = 4
 ERR_PARSE, ERR_IO, PARSE_FLUSH, PARSE_HOGWILD_LOAD = 6, 7, 100, 101
 FFM_F32, FFM_F16_BUCKETS = 0, 1  # fwgpu_ffm_storage
 OPT_SGD, OPT_ADAGRAD_FLEX, OPT_ADAGRAD_LUT = 100, 200, 300
@@ -25,6 +26,8 @@ TABLE_LR, TABLE_FFM_W, TABLE_FFM_ACC, TABLE_NN_W, TABLE_NN_ACC = 0, 1, 2, 3, 4
 ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK = 0, 1, 2, 3, 4, 5
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
+CANDIDATE_INFO = np.dtype([("code", "<i4"), ("is_delta", "u1"), ("record_ok", "u1"), ("by_host", "u1"), ("pad", "u1"), ("n_lr", "<u4"),
+                           ("n_ffm", "<u4")])  # fwgpu_candidate_info
 LR_ENTRY = np.dtype([("hash", "<u4"), ("value", "<f4"), ("combo_index", "<u4")])
 FFM_ENTRY = np.dtype([("hash", "<u4"), ("value", "<f4"), ("contra_field_index", "<u4")])
 
@@ -127,6 +130,8 @@ def lib():
         "fwgpu_predict_with_cache": [vp, vp, vp, u32, vp, u32, P(f32)],
         "fwgpu_block_cache_filter": [vp, vp, u32, vp, P(u32)],
         "fwgpu_block_cache_free": [vp],
+        "fwgpu_block_cache_cover_record": [vp, P(TranslatorConfig), vp, u32],
+        "fwgpu_block_cache_record_ok": [vp, P(TranslatorConfig), vp, u32],
         "fwgpu_batch_set_cache": [vp, vp],
         "fwgpu_dist_unique_id": [vp, u64],
         "fwgpu_dist_init": [vp, vp, i32, i32, P(vp)],
@@ -217,6 +222,7 @@ def lib():
         "fwgpu_text_parser_create": [vp, i32, P(vp)],
         "fwgpu_text_parser_parse_buffer": [vp, C.c_char_p, u64, vp, u64, vp, u64, P(u64), P(u64), P(u64)],
         "fwgpu_text_parser_last_lines": [vp, P(u64), P(u64)],
+        "fwgpu_text_parser_parse_candidates": [vp, vp, vp, P(TranslatorConfig), C.c_char_p, u64, u64, vp, u64, vp, vp, P(u64), P(u64)],
         "fwgpu_record_batch_from_text": [vp, P(TranslatorConfig), vp, C.c_char_p, u64, u64, P(vp), P(u64), P(u64)],
         "fwgpu_f32_from_text": [C.c_char_p, u64, P(f32), P(i32)],
         "fwgpu_mi_from_json": [C.c_char_p, u64, P(vp)],

@@ -539,6 +539,18 @@ int block_cache_record_ok(const fwgpu_block_cache *c, const fwgpu_translator_con
 // the same for a candidate-only record on top of its context's record (ctx may be NULL)
 int count_record(const fwgpu_translator_config *t, const uint32_t *rec, uint32_t rec_len, const uint32_t *ctx, uint32_t ctx_len,
                  uint32_t *n_lr, uint32_t *n_ffm);
+// Serving from text (text_parser.cpp).  text_lines_scan: status passes over every line of `text` -- candidates of the context `px` / `cache`
+// hold, or whole lines when px is NULL -- with per-line codes, lengths, entry counts and the cache's record rule; the text stays on the device.
+// text_lines_place then writes the records to d_records + rec_off[line] (device memory) and returns when they are there.  piece_bytes: text per
+// pass (0: the parser's own).  zero_word1: every record's label word is 0, as serving sends it.  *out points into the parser until its next call.
+struct TextLines {
+    const fwgpu_candidate_info *info = nullptr;
+    const uint64_t *rec_off = nullptr;
+    uint64_t n_lines = 0, n_words = 0;
+};
+int text_lines_scan(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache, const fwgpu_translator_config *t,
+                    const char *text, uint64_t len, uint64_t piece_bytes, bool zero_word1, TextLines *out);
+int text_lines_place(fwgpu_text_parser *tp, uint32_t *d_records);
 // device-resident raw-record batch (translation happens inside the example kernel)
 int record_batch_alloc(fwgpu_regressor *r, const fwgpu_translator_config *t, uint32_t n_cap, uint64_t words_cap,
                        fwgpu_batch **out, bool host_mapped = false);

@@ -14,6 +14,14 @@
 // behind the FFM block inherits forward_with_cache): the cache also keeps how many features it holds per field, which is what the head's input diagonal
 // needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (regressor.cpp run_batch_head_predict), a smaller one
 // the per-example kernel.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result.
+//
+// fwgpu_predictor_predict_text takes a request as one text, a candidate per line, and keeps the host out of the scan: the device parser
+// (textparse.hip, candidate mode) turns every line that starts with '|' into the candidate-only record fwgpu_parser_parse_candidate defines,
+// counts its entries and decides the cache's record rule; its write pass puts the records straight into the shared record batch, and the one
+// launch fwgpu_predictor_predict_batch makes follows.  Lines the kernel does not take are parsed here and copied in.  A request in which some
+// line's record breaks the record rule or cannot be split off the context, a predictor without a device cache (packed weights, FFM-less models,
+// no fw_setup_cache yet) or with a context that is not its own record, and FWGPU_SERVING_HOST_PARSE=1 take fwgpu_predictor_predict_batch on
+// the split lines instead (fwgpu_predictor_last_text_route: fell_back).  FWGPU_SERVING_TEXT_PIECE=<bytes>: text per parser pass.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -39,7 +47,9 @@ struct SharedModel {  // what clone_lite shares: the immutable regressor and the
     std::mutex mu;  // the regressor's single-example staging buffers are shared
     fwgpu_batch *batch = nullptr;  // device buffers of fwgpu_predictor_predict_batch, grown on demand and reused
     fwgpu_batch *one = nullptr;    // single requests: a host-mapped batch (no copy calls, no memset: launch + one synchronisation)
+    fwgpu_text_parser *tp = nullptr;  // fwgpu_predictor_predict_text: the device parser, made by the first call, used under mu
     ~SharedModel() {
+        if (tp) fwgpu_text_parser_free(tp);
         if (batch) fwgpu_batch_free(batch);
         if (one) fwgpu_batch_free(one);
         if (re) fwgpu_free(re);
@@ -121,6 +131,8 @@ struct FfiPredictor {
     std::vector<uint32_t> record;
     std::vector<fwgpu_lr_entry> lr;
     std::vector<fwgpu_ffm_entry> ffm;
+    uint64_t text_lines = 0, text_host_lines = 0;  // fwgpu_predictor_last_text_route
+    int text_fell_back = 0;
     ~FfiPredictor() {
         if (prefix) fwgpu_parse_prefix_free(prefix);
         if (parser) fwgpu_parser_free(parser);
@@ -512,6 +524,124 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
     if (rc != FWGPU_OK) return rc;
     for (size_t j = 0; j < slot.size(); j++) out[slot[j]] = preds[j];
     lap("predicted");
+    return FWGPU_OK;
+}
+
+// fwgpu_predictor_predict_text by the existing route: the lines, each with its newline, through fwgpu_predictor_predict_batch
+static int predict_text_by_lines(FfiPredictor *p, const char *text, uint64_t len, int with_cache, float *out, uint64_t cap, uint64_t *n) {
+    std::vector<std::string> lines;
+    for (uint64_t pos = 0; pos < len;) {
+        const char *e = static_cast<const char *>(std::memchr(text + pos, '\n', len - pos));
+        const uint64_t size = e ? (uint64_t)(e - (text + pos)) + 1 : len - pos;
+        lines.emplace_back(text + pos, size);
+        if (!e) lines.back().push_back('\n');
+        pos += size;
+    }
+    p->text_lines = p->text_host_lines = lines.size();
+    p->text_fell_back = 1;
+    *n = lines.size();
+    if (lines.size() > cap || lines.size() > 0xffffffffull) return fail(FWGPU_ERR_RANGE, "predict_text: more lines than the output holds");
+    std::vector<const char *> ptrs(lines.size());
+    for (size_t i = 0; i < lines.size(); i++) ptrs[i] = lines[i].c_str();
+    return fwgpu_predictor_predict_batch(p, ptrs.data(), (uint32_t)ptrs.size(), with_cache, out);
+}
+
+// A request as one text, one candidate per line: out[i] is what fw_predict_with_cache (with_cache != 0) or fw_predict would return for line i
+// with its newline, *n the number of lines.  See the head of this file for the route.
+int fwgpu_predictor_predict_text(FfiPredictor *ptr, const char *text, uint64_t len, int with_cache, float *out, uint64_t cap, uint64_t *n) {
+    if (!ptr || (!text && len) || (!out && cap) || !n) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *n = 0;
+    ptr->text_lines = ptr->text_host_lines = 0;
+    ptr->text_fell_back = 0;
+    if (len == 0) return FWGPU_OK;
+    SharedModel &m = *ptr->model;
+    const bool cand = with_cache != 0;
+    if (std::getenv("FWGPU_SERVING_HOST_PARSE") || (cand && !(ptr->cache && ptr->prefix && ptr->delta_ok)))
+        return predict_text_by_lines(ptr, text, len, with_cache, out, cap, n);
+    std::string owned;
+    if (text[len - 1] != '\n') {  // the last line gets its newline, as every line a caller of fw_predict sends has one
+        owned.assign(text, len);
+        owned.push_back('\n');
+        text = owned.data();
+        len++;
+    }
+    const char *piece_env = std::getenv("FWGPU_SERVING_TEXT_PIECE");
+    const uint64_t piece = piece_env && std::atoll(piece_env) > 0 ? (uint64_t)std::atoll(piece_env) : 0;
+    std::unique_lock<std::mutex> g(m.mu);
+    int rc = FWGPU_OK;
+    if (!m.tp && (rc = fwgpu_text_parser_create(m.vw, m.re->device, &m.tp)) != FWGPU_OK) return rc;
+    TextLines tl;
+    if ((rc = text_lines_scan(m.tp, cand ? ptr->prefix : nullptr, cand ? ptr->cache : nullptr, &m.tr, text, len, piece, /*zero_word1=*/true, &tl)) != FWGPU_OK)
+        return rc;
+    uint64_t host_lines = 0;
+    (void)fwgpu_text_parser_last_lines(m.tp, nullptr, &host_lines);
+    const uint32_t ctx_len = cand ? (uint32_t)ptr->cache->ctx_rec.size() : 0;
+    RecordStats stats;
+    std::vector<uint64_t> off(1, 0);
+    std::vector<uint64_t> slot;  // which line each record belongs to
+    bool by_lines = false;
+    for (uint64_t i = 0; i < tl.n_lines && !by_lines; i++) {
+        const fwgpu_candidate_info &li = tl.info[i];
+        const uint64_t nw = tl.rec_off[i + 1] - tl.rec_off[i];
+        if (li.code != FWGPU_OK || nw == 0) continue;
+        if (!li.record_ok || (cand && !li.is_delta)) {  // the rule fwgpu_predictor_predict_batch has: the whole request goes the other way
+            by_lines = true;
+            break;
+        }
+        stats.max_lr = std::max(stats.max_lr, li.n_lr);
+        stats.max_ffm = std::max(stats.max_ffm, li.n_ffm);
+        stats.max_rec = std::max(stats.max_rec, (uint32_t)nw + ctx_len);  // (LDS holds the context's record behind the candidate's)
+        stats.tot_lr += li.n_lr;
+        stats.tot_ffm += li.n_ffm;
+        off.push_back(tl.rec_off[i + 1]);
+        slot.push_back(i);
+    }
+    if (by_lines || tl.n_lines > 0xffffffffull) {
+        g.unlock();
+        return predict_text_by_lines(ptr, text, len, with_cache, out, cap, n);
+    }
+    *n = tl.n_lines;
+    ptr->text_lines = tl.n_lines;
+    ptr->text_host_lines = host_lines;
+    if (tl.n_lines > cap) return fail(FWGPU_ERR_RANGE, "predict_text: more lines than the output holds");
+    for (uint64_t i = 0; i < tl.n_lines; i++) out[i] = kExceptionErrorCode;
+    if (slot.empty()) return FWGPU_OK;
+    const uint32_t nrec = (uint32_t)slot.size();
+    const uint64_t total_words = tl.n_words;
+    if (!m.batch || m.batch->n_cap < nrec || m.batch->words_cap < total_words) {
+        if (m.batch) fwgpu_batch_free(m.batch);
+        m.batch = nullptr;
+        if ((rc = record_batch_alloc(m.re, &m.tr, std::max<uint32_t>(nrec * 2, 256), std::max<uint64_t>(total_words * 2, 1 << 16), &m.batch)) != FWGPU_OK) return rc;
+    }
+    fwgpu_batch *b = m.batch;
+    if ((rc = text_lines_place(m.tp, b->records)) != FWGPU_OK) return rc;  // write pass + the host-parsed records; the records are there on return
+    if (hipMemcpyAsync(b->rec_off, off.data(), ((size_t)nrec + 1) * 8, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+        return fail(FWGPU_ERR_DEVICE, "predict_text: copy to the device failed");
+    b->n = nrec;
+    b->n_lr = stats.tot_lr;
+    b->n_ffm = stats.tot_ffm;
+    b->n_words = total_words;
+    b->max_lr = m.re->cfg.wiring == FWGPU_WIRING_FFM_ONLY ? 0 : stats.max_lr;
+    b->max_ffm = stats.max_ffm;
+    b->max_rec = stats.max_rec;
+    b->aligned4 = true;
+    if (cand) rc = fwgpu_batch_set_cache(b, ptr->cache);
+    b->delta_records = cand;
+    if (rc == FWGPU_OK) rc = fwgpu_learn_batch(m.re, b, FWGPU_MODE_HOGWILD, /*update=*/0, nullptr);
+    std::vector<float> preds(nrec);
+    if (rc == FWGPU_OK) rc = fwgpu_batch_predictions(b, preds.data(), nrec, nullptr);
+    (void)fwgpu_batch_set_cache(b, nullptr);
+    b->delta_records = false;
+    if (rc != FWGPU_OK) return rc;
+    for (size_t j = 0; j < slot.size(); j++) out[slot[j]] = preds[j];
+    return FWGPU_OK;
+}
+
+int fwgpu_predictor_last_text_route(const FfiPredictor *ptr, uint64_t *lines, uint64_t *host_lines, int *fell_back) {
+    if (!ptr) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (lines) *lines = ptr->text_lines;
+    if (host_lines) *host_lines = ptr->text_host_lines;
+    if (fell_back) *fell_back = ptr->text_fell_back;
     return FWGPU_OK;
 }
 

@@ -45,11 +45,17 @@ struct HostRecord {
     std::vector<uint32_t> words;
 };
 
+struct LineMode {  // what the kernels get beyond the text: all zero for fwgpu_text_parser_parse_buffer
+    TextTranslator tr{};
+    TextCandidate cand{};
+    uint32_t set_word1 = 0, word1 = 0;
+};
+
 struct TextChunk {  // one chunk of text on the device and what the host knows about its lines
     DevBuf text, cnt, rank, lstart, status, off, long_list;
     uint32_t len = 0, nlines = 0, n_used = 0;
     uint64_t first_word = 0;  // offset of the chunk's first record
-    std::vector<uint2> h_status;
+    std::vector<uint4> h_status;
     std::vector<uint32_t> h_lstart;  // fetched only when a line needs the host or the call stops inside the chunk
     std::vector<uint64_t> h_off;
     std::vector<HostRecord> host_recs;
@@ -73,6 +79,13 @@ struct fwgpu_text_parser {
     std::vector<std::unique_ptr<TextChunk>> chunks;
     std::vector<uint32_t> line_words;  // one host-parsed record
     uint64_t last_lines = 0, last_host_lines = 0;
+    // candidate / counting calls: the translator and the cache's keys on the device (uploaded again only when they change), and the call's results
+    LineMode mode{};
+    DevBuf side;
+    std::vector<unsigned char> side_host;
+    std::vector<uint64_t> li_off;
+    std::vector<fwgpu_candidate_info> li_info;
+    size_t li_chunks = 0;
 };
 
 namespace fwgpu {
@@ -117,7 +130,7 @@ int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail) {
     ch.h_lstart.clear();
     ch.host_recs.clear();
     ch.n_used = 0;
-    if (!(rc = ch.lstart.ensure(4 * ((size_t)ch.nlines + 2)))) rc = ch.status.ensure(8 * std::max<size_t>(ch.nlines, 1));
+    if (!(rc = ch.lstart.ensure(4 * ((size_t)ch.nlines + 2)))) rc = ch.status.ensure(16 * std::max<size_t>(ch.nlines, 1));
     if (!rc) rc = ch.off.ensure(8 * std::max<size_t>(ch.nlines, 1));
     if (!rc) rc = ch.long_list.ensure(4 * std::max<size_t>(ch.nlines, 1));
     if (rc) return rc;
@@ -127,12 +140,14 @@ int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail) {
     a.lstart = ch.lstart.as<uint32_t>();
     a.nlines = ch.nlines;
     a.ns = tp->ns;
-    a.status = ch.status.as<uint2>();
+    a.tr = tp->mode.tr;
+    a.cand = tp->mode.cand;
+    a.status = ch.status.as<uint4>();
     a.long_list = ch.long_list.as<uint32_t>();
     a.long_count = tp->long_count;
     FWGPU_HIP(text_parse_launch(a, false, tp->stream));
     ch.h_status.resize(ch.nlines);
-    if (ch.nlines) FWGPU_HIP(hipMemcpyAsync(ch.h_status.data(), ch.status.p, 8 * (size_t)ch.nlines, hipMemcpyDeviceToHost, tp->stream));
+    if (ch.nlines) FWGPU_HIP(hipMemcpyAsync(ch.h_status.data(), ch.status.p, 16 * (size_t)ch.nlines, hipMemcpyDeviceToHost, tp->stream));
     FWGPU_HIP(hipStreamSynchronize(tp->stream));
     return FWGPU_OK;
 }
@@ -168,7 +183,11 @@ int chunk_write(fwgpu_text_parser *tp, TextChunk &ch, uint32_t *dst, uint64_t re
     a.lstart = ch.lstart.as<uint32_t>();
     a.nlines = ch.nlines;
     a.ns = tp->ns;
-    a.status = ch.status.as<uint2>();
+    a.tr = tp->mode.tr;
+    a.cand = tp->mode.cand;
+    a.set_word1 = tp->mode.set_word1;
+    a.word1 = tp->mode.word1;
+    a.status = ch.status.as<uint4>();
     a.n_used = ch.n_used;
     a.dst_off = ch.off.as<uint64_t>();
     a.dst = dst;
@@ -184,6 +203,7 @@ int run(fwgpu_text_parser *tp, const char *text, uint64_t len, uint32_t *words, 
         bool keep, RunResult &R) {
     FWGPU_HIP(hipSetDevice(tp->device));
     tp->last_lines = tp->last_host_lines = 0;
+    tp->mode = LineMode();
     uint64_t pos = 0, nr = 0, nw = 0;
     bool stop = false;
     auto set_off = [&](uint64_t i, uint64_t v) {
@@ -235,7 +255,7 @@ int run(fwgpu_text_parser *tp, const char *text, uint64_t len, uint32_t *words, 
             if (nr == max_records) break;
             uint64_t reclen = ch.h_status[i].y;
             tp->last_lines++;
-            if (ch.h_status[i].x != kTextDeviceOk) {
+            if ((ch.h_status[i].x & 0xffu) != kTextDeviceOk) {
                 if ((rc = fetch_line_starts(tp, ch))) return rc;
                 rc = host_line(tp, text + pos + ch.h_lstart[i], ch.h_lstart[i + 1] - ch.h_lstart[i]);
                 if (rc != FWGPU_OK) {
@@ -281,6 +301,200 @@ int run(fwgpu_text_parser *tp, const char *text, uint64_t len, uint32_t *words, 
     return FWGPU_OK;
 }
 
+
+// ---- every line of a text: a request's candidates, or whole lines, with the per-line facts serving needs
+
+// the translator's CSR arrays and the cache's keys, as the kernels read them; kept on the device between calls that bring the same ones
+int upload_side(fwgpu_text_parser *tp, const fwgpu_translator_config *t, const fwgpu_block_cache *cache) {
+    const uint32_t nns = tp->ns.num_namespaces;
+    const uint32_t ncm = t->n_combos ? t->combo_off[t->n_combos] : 0;
+    const uint32_t npr = (t->ffm_k && t->n_fields) ? t->field_off[t->n_fields] : 0;
+    for (uint32_t m = 0; m < ncm; m++)
+        if (t->combo_ns[m] >= nns) return fail(FWGPU_ERR_INVALID, "translator: a combo names a namespace the map does not have");
+    for (uint32_t m = 0; m < npr; m++)
+        if (t->field_ns[m] >= nns) return fail(FWGPU_ERR_INVALID, "translator: a field names a namespace the map does not have");
+    const size_t np = cache ? cache->present.size() : 0;
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    size_t q = 0;
+    const size_t q_coff = q; q = up(q + 4 * ((size_t)t->n_combos + 1));
+    const size_t q_cns = q; q = up(q + 4 * (size_t)ncm);
+    const size_t q_pns = q; q = up(q + 4 * (size_t)npr);
+    const size_t q_pfk = q; q = up(q + 4 * (size_t)npr);
+    const size_t q_pres = q; q = up(q + 8 * np);
+    std::vector<unsigned char> blob(std::max<size_t>(q, 16), 0);
+    if (t->n_combos) std::memcpy(blob.data() + q_coff, t->combo_off, 4 * ((size_t)t->n_combos + 1));
+    if (ncm) std::memcpy(blob.data() + q_cns, t->combo_ns, 4 * (size_t)ncm);
+    if (npr) {
+        std::memcpy(blob.data() + q_pns, t->field_ns, 4 * (size_t)npr);
+        uint32_t *fk = reinterpret_cast<uint32_t *>(blob.data() + q_pfk);
+        for (uint32_t f = 0; f < t->n_fields; f++)
+            for (uint32_t m = t->field_off[f]; m < t->field_off[f + 1]; m++) fk[m] = f * t->ffm_k;
+    }
+    if (np) std::memcpy(blob.data() + q_pres, cache->present.data(), 8 * np);
+    if (blob != tp->side_host || !tp->side.p) {
+        int rc = tp->side.ensure(blob.size());
+        if (rc) return rc;
+        FWGPU_HIP(hipMemcpy(tp->side.p, blob.data(), blob.size(), hipMemcpyHostToDevice));  // (no pass of an earlier call is in flight)
+        tp->side_host = blob;
+    }
+    const unsigned char *b = tp->side.as<unsigned char>();
+    LineMode &lm = tp->mode;
+    lm.tr.combo_off = reinterpret_cast<const uint32_t *>(b + q_coff);
+    lm.tr.combo_ns = reinterpret_cast<const uint32_t *>(b + q_cns);
+    lm.tr.pair_ns = reinterpret_cast<const uint32_t *>(b + q_pns);
+    lm.tr.pair_fk = reinterpret_cast<const uint32_t *>(b + q_pfk);
+    lm.tr.n_combos = t->n_combos;
+    lm.tr.n_pairs = npr;
+    lm.tr.add_const = t->add_constant_feature ? 1 : 0;
+    lm.tr.ffm_mask = ffm_hash_mask(t->ffm_bit_precision, t->ffm_k);
+    if (cache) {
+        lm.cand.ctx_rec = cache->d_ctx_rec;
+        lm.cand.ctx_len = (uint32_t)cache->ctx_rec.size();
+        lm.cand.cover = cache->d_cover;
+        lm.cand.n_cover_slots = (uint32_t)cache->ctx_slots.size();
+        lm.cand.present = reinterpret_cast<const uint64_t *>(b + q_pres);
+        lm.cand.n_present = (uint32_t)np;
+    }
+    return FWGPU_OK;
+}
+
+// one line by the host parser, with the host twins of the kernel's per-line facts; the record (none for an error) is left in tp->line_words
+void host_fact_line(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache, const fwgpu_translator_config *t,
+                    const char *line, uint64_t size, fwgpu_candidate_info *info) {
+    const size_t ctx_len = cache ? cache->ctx_rec.size() : 0;
+    tp->line_words.resize((size_t)size + ctx_len + tp->ns.num_namespaces + 16);  // header + slots + one word per byte, behind the context's words when merged
+    uint32_t nw = 0;
+    int is_delta = 0;
+    const int rc = px ? fwgpu_parser_parse_candidate(tp->host, px, line, size, tp->line_words.data(), (uint32_t)tp->line_words.size(), &nw, &is_delta)
+                      : fwgpu_parser_parse_line(tp->host, line, size, tp->line_words.data(), (uint32_t)tp->line_words.size(), &nw);
+    *info = fwgpu_candidate_info{};
+    info->code = rc;
+    info->by_host = 1;
+    tp->last_host_lines++;
+    if (rc != FWGPU_OK) nw = 0;
+    tp->line_words.resize(nw);
+    if (!nw) return;
+    info->is_delta = is_delta ? 1 : 0;
+    uint32_t *rec = tp->line_words.data();
+    if (tp->mode.set_word1) rec[1] = tp->mode.word1;
+    uint32_t n_lr = 0, n_ffm = 0;
+    const bool counted = count_record(t, rec, nw, is_delta ? cache->ctx_rec.data() : nullptr, is_delta ? (uint32_t)ctx_len : 0, &n_lr, &n_ffm) == FWGPU_OK;
+    info->n_lr = counted ? n_lr : 0;
+    info->n_ffm = counted ? n_ffm : 0;
+    info->record_ok = counted && (!px || block_cache_record_ok(cache, t, rec, nw, is_delta != 0)) ? 1 : 0;
+}
+
+// Status passes over every line of `text`, piece by piece (pieces are cut at line breaks and stay on the device: tp->chunks[0 .. li_chunks)).
+// px != NULL: the lines are candidates of the context `px` and `cache` hold.  Leaves tp->li_off (n_lines + 1 word offsets) and tp->li_info.
+int scan_lines(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache, const fwgpu_translator_config *t, const char *text,
+               uint64_t len, uint64_t piece_bytes) {
+    tp->last_lines = tp->last_host_lines = 0;
+    tp->li_off.assign(1, 0);
+    tp->li_info.clear();
+    tp->li_chunks = 0;
+    piece_bytes = std::min<uint64_t>(std::max<uint64_t>(piece_bytes, 1), kChunkBytes);
+    uint64_t pos = 0, nw = 0;
+    auto next_chunk = [&]() -> TextChunk & {
+        if (tp->li_chunks == tp->chunks.size()) tp->chunks.emplace_back(new TextChunk());
+        TextChunk &ch = *tp->chunks[tp->li_chunks++];
+        ch.nlines = ch.n_used = ch.len = 0;
+        ch.host_recs.clear();
+        ch.h_lstart.clear();
+        return ch;
+    };
+    fwgpu_candidate_info info;
+    auto host_line_at = [&](TextChunk &ch, uint32_t i, const char *line, uint64_t size) {
+        host_fact_line(tp, px, cache, t, line, size, &info);
+        if (!tp->line_words.empty()) ch.host_recs.push_back({i, nw, tp->line_words});
+        return (uint64_t)tp->line_words.size();
+    };
+    while (pos < len) {
+        uint64_t cut = std::min<uint64_t>(len - pos, piece_bytes);
+        if (pos + cut < len) {
+            const void *nl = memrchr(text + pos, '\n', cut);
+            if (!nl) {  // one line longer than a piece: the host's
+                const char *e = static_cast<const char *>(std::memchr(text + pos + cut, '\n', len - pos - cut));
+                const uint64_t size = e ? (uint64_t)(e - (text + pos)) + 1 : len - pos;
+                nw += host_line_at(next_chunk(), 0, text + pos, size);
+                tp->li_info.push_back(info);
+                tp->li_off.push_back(nw);
+                tp->last_lines++;
+                pos += size;
+                continue;
+            }
+            cut = (uint64_t)(static_cast<const char *>(nl) - (text + pos)) + 1;
+        }
+        TextChunk &ch = next_chunk();
+        int rc = upload_text(tp, ch, text + pos, (uint32_t)cut);
+        if (!rc) rc = chunk_status(tp, ch, text[pos + cut - 1] != '\n');
+        if (rc) return rc;
+        ch.first_word = nw;
+        ch.h_off.resize(ch.nlines);
+        for (uint32_t i = 0; i < ch.nlines; i++) {
+            const uint4 st = ch.h_status[i];
+            ch.h_off[i] = nw;
+            if ((st.x & 0xffu) == kTextDeviceOk) {
+                info = fwgpu_candidate_info{};
+                info.code = FWGPU_OK;
+                info.is_delta = px ? 1 : 0;
+                info.record_ok = (!px || (st.x & kTextRecordOk)) ? 1 : 0;
+                info.n_lr = st.z;
+                info.n_ffm = st.w;
+                nw += st.y;
+            } else {
+                if ((rc = fetch_line_starts(tp, ch))) return rc;
+                nw += host_line_at(ch, i, text + pos + ch.h_lstart[i], ch.h_lstart[i + 1] - ch.h_lstart[i]);
+            }
+            tp->li_info.push_back(info);
+            tp->li_off.push_back(nw);
+        }
+        tp->last_lines += ch.nlines;
+        ch.n_used = ch.nlines;
+        pos += cut;
+    }
+    return FWGPU_OK;
+}
+
+}  // namespace
+
+int text_lines_scan(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache, const fwgpu_translator_config *t, const char *text,
+                    uint64_t len, uint64_t piece_bytes, bool zero_word1, TextLines *out) {
+    if (!tp || !t || !out || (!text && len) || (px && !cache)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (px) {
+        if (!cache->d_cover) return fail(FWGPU_ERR_INVALID, "candidates from text: the cache does not know its context's record (fwgpu_block_cache_cover_record)");
+        if (cache->owner->device != tp->device) return fail(FWGPU_ERR_INVALID, "candidates from text: parser and cache are on different devices");
+        if (!fwgpu_parse_prefix_is_record(px, cache->ctx_rec.data(), (uint32_t)cache->ctx_rec.size()) ||
+            cache->ctx_rec.size() < 3 + (size_t)tp->ns.num_namespaces)
+            return fail(FWGPU_ERR_INVALID, "candidates from text: the prefix is not the record of the cache's context (fwgpu_parse_prefix_is_record)");
+    }
+    FWGPU_HIP(hipSetDevice(tp->device));
+    tp->mode = LineMode();
+    int rc = upload_side(tp, t, px ? cache : nullptr);
+    if (rc) return rc;
+    tp->mode.set_word1 = zero_word1 ? 1 : 0;
+    rc = scan_lines(tp, px, cache, t, text ? text : "", len, piece_bytes ? piece_bytes : kChunkBytes);
+    if (rc) return rc;
+    out->info = tp->li_info.data();
+    out->rec_off = tp->li_off.data();
+    out->n_lines = tp->li_info.size();
+    out->n_words = tp->li_off.back();
+    return FWGPU_OK;
+}
+
+int text_lines_place(fwgpu_text_parser *tp, uint32_t *d_records) {
+    FWGPU_HIP(hipSetDevice(tp->device));
+    for (size_t c = 0; c < tp->li_chunks; c++) {
+        TextChunk &ch = *tp->chunks[c];
+        int rc = chunk_write(tp, ch, d_records, 0);
+        if (rc) return rc;
+        for (const HostRecord &h : ch.host_recs)
+            FWGPU_HIP(hipMemcpyAsync(d_records + h.off, h.words.data(), h.words.size() * 4, hipMemcpyHostToDevice, tp->stream));
+    }
+    FWGPU_HIP(hipStreamSynchronize(tp->stream));
+    return FWGPU_OK;
+}
+
+namespace {
 }  // namespace
 }  // namespace fwgpu
 
@@ -377,6 +591,32 @@ int fwgpu_text_parser_parse_buffer(fwgpu_text_parser *tp, const char *text, uint
     *n_words = R.n_words;
     *consumed = R.consumed;
     return R.rc;
+}
+
+// Every line of `text` as a candidate of the context that `px` scanned and `cache` holds: fwgpu_parser_parse_candidate line by line, with the scan of
+// the lines that start with '|' done by the device, and per line the entry counts and the cache's record rule (include/fwgpu.h).
+int fwgpu_text_parser_parse_candidates(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache,
+                                       const fwgpu_translator_config *t, const char *text, uint64_t len, uint64_t max_lines, uint32_t *words,
+                                       uint64_t words_cap, uint64_t *rec_off, fwgpu_candidate_info *info, uint64_t *n_lines, uint64_t *n_words) {
+    if (!tp || !px || !cache || !t || (!text && len) || (!words && words_cap) || !rec_off || (!info && max_lines) || !n_lines || !n_words)
+        return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *n_lines = *n_words = 0;
+    rec_off[0] = 0;
+    TextLines tl;
+    int rc = text_lines_scan(tp, px, cache, t, text, len, 0, false, &tl);
+    if (rc) return rc;
+    if (tl.n_lines > max_lines) return fail(FWGPU_ERR_RANGE, "parse_candidates: more lines than max_lines");
+    if (tl.n_words > words_cap) return fail(FWGPU_ERR_RANGE, "parse_candidates: record buffer too small");
+    if (tl.n_words) {
+        if ((rc = tp->words.ensure(4 * (size_t)tl.n_words))) return rc;
+        if ((rc = text_lines_place(tp, tp->words.as<uint32_t>()))) return rc;
+        FWGPU_HIP(hipMemcpy(words, tp->words.p, 4 * (size_t)tl.n_words, hipMemcpyDeviceToHost));
+    }
+    std::memcpy(rec_off, tl.rec_off, 8 * ((size_t)tl.n_lines + 1));
+    if (tl.n_lines) std::memcpy(info, tl.info, sizeof(fwgpu_candidate_info) * (size_t)tl.n_lines);
+    *n_lines = tl.n_lines;
+    *n_words = tl.n_words;
+    return FWGPU_OK;
 }
 
 int fwgpu_text_parser_last_lines(const fwgpu_text_parser *tp, uint64_t *lines, uint64_t *host_lines) {

@@ -12,6 +12,12 @@
 // The kernel never guesses: whatever is not a plain example it reproduces exactly gets NEEDS_HOST and the host parser takes the line.
 // Lines up to 4 KiB run four waves to a workgroup; longer ones (to 64 KiB) are listed and taken by single-wave workgroups with a larger
 // LDS image.  The same code runs twice: once for {status, length}, once -- when the host has placed the records -- to write them.
+//
+// Candidate mode (TextParseArgs::cand): the lines are the candidates of one context whose record the device holds.  A line that starts with
+// '|' opens a namespace of its own, so the scan does not depend on the context and its record is the stand-alone one with the context's
+// words 1 and 2 and NO_FEATURES in every slot whose merged form equals the context's slot word -- fwgpu_parser_parse_candidate's
+// candidate-only record (parser.cpp).  With a translator (TextParseArgs::tr) the status pass also counts the line's LR and FFM entries
+// (translate.cpp count_record) and, in candidate mode, decides the cache's record rule (regressor.cpp block_cache_record_ok) exactly.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -100,11 +106,37 @@ struct LineLds {
     uint32_t *tok_a;    // namespace: entry; feature: hash
     uint32_t *tok_w;    // feature: bits of ns_weight * weight, or of the f32 value
     uint32_t *slots;    // [kTextMaxNamespaces]
+    uint16_t *slot_run; // [kTextMaxNamespaces] first feature token of the run a filled slot holds
 };
 
-// One line by one wave.  Returns the status (wave-uniform); *len_out = record length.  WRITE: `dst` is where the record goes.
-template <int TOKCAP, bool WRITE>
-__device__ uint32_t parse_line_wave(const TextParseArgs &a, uint32_t start, uint32_t size, const LineLds &L, uint32_t *dst, uint32_t *len_out) {
+struct LineFacts {  // what the status pass reports beside the status
+    uint32_t len = 0, n_lr = 0, n_ffm = 0;
+    bool record_ok = false;
+};
+
+__device__ inline uint32_t wave_sum(uint32_t v) {
+    for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+
+// is (hash & mask, field * k) a cached feature: fwgpu_block_cache::present is sorted
+__device__ inline bool present_dev(const TextCandidate &cd, uint32_t masked_hash, uint32_t fk) {
+    const uint64_t key = ((uint64_t)masked_hash << 32) | fk;
+    uint32_t lo = 0, hi = cd.n_present;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const uint64_t v = cd.present[mid];
+        if (v == key) return true;
+        if (v < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+// One line by one wave.  Returns the status (wave-uniform); *facts: record length, entry counts, record rule.  WRITE: `dst` is where the record goes.
+// CAND: the line is a candidate of a.cand's context.
+template <int TOKCAP, bool WRITE, bool CAND>
+__device__ uint32_t parse_line_wave(const TextParseArgs &a, uint32_t start, uint32_t size, const LineLds &L, uint32_t *dst, LineFacts *facts) {
     const uint32_t lane = threadIdx.x & 63u;
     const TextNsTable &ns = a.ns;
     const uint32_t rowlen = size - 1;  // "ignore last newline byte": the line's last byte only ever answers the one-past reads
@@ -118,6 +150,7 @@ __device__ uint32_t parse_line_wave(const TextParseArgs &a, uint32_t start, uint
     // ---- head (parser.rs:226-316)
     const unsigned char c0 = c[0];
     if (c0 != '1' && c0 != '-' && c0 != '|') return kTextNeedsHost;  // commands and errors
+    if (CAND && c0 != '|') return kTextNeedsHost;  // a label, or a feature token that goes on in the context's last namespace
     const uint32_t label = c0 == '1' ? 1u : c0 == '-' ? 0u : kNoLabel;
     uint32_t imp = kFloatOne, ie = 0;
     if (c0 != '|') {
@@ -231,6 +264,7 @@ __device__ uint32_t parse_line_wave(const TextParseArgs &a, uint32_t start, uint
             ns_start = len;
             continue;
         }
+        if (ns_count == 0) L.slot_run[ns_slot] = (uint16_t)t;
         if (kind == 1 && ns_count == 0) {
             L.slots[ns_slot] = av;
         } else {
@@ -246,13 +280,62 @@ __device__ uint32_t parse_line_wave(const TextParseArgs &a, uint32_t start, uint
         ns_count++;
     }
     if (len > 65535u) return kTextNeedsHost;  // the slot word has 16 bits for a position
-    *len_out = len;
-    if (WRITE) {
+    const bool count = !WRITE && a.tr.combo_off != nullptr;
+    // entry counts read 14-bit start positions; in the context's record + this one a range lies ctx_len - (header + slots) further on
+    if ((CAND || count) && (CAND ? a.cand.ctx_len - (kHeaderLen + nns) : 0u) + len > 16383u) return kTextNeedsHost;
+    facts->len = len;
+    wave_sync();
+    if (CAND) {  // a single feature the context's slot already holds: "as in the context"
+        for (uint32_t j = lane; j < nns; j += 64) {
+            const uint32_t w = L.slots[j];
+            if ((w & kNotSingle) == 0 && w == a.cand.ctx_rec[kHeaderLen + j]) L.slots[j] = kNoFeatures;
+        }
         wave_sync();
+    }
+    if (count) {
+        const TextTranslator &tr = a.tr;
+        auto cnt = [&](uint32_t nsi) -> uint32_t {
+            uint32_t w = L.slots[nsi];
+            if (CAND && w == kNoFeatures) w = a.cand.ctx_rec[kHeaderLen + nsi];  // inherited
+            if ((w & kNotSingle) == 0) return 1u;
+            return ((w & 0xffffu) - ((w >> 16) & 0x3fffu)) >> 1;
+        };
+        constexpr unsigned long long kCap = 2000000ull;  // count_record refuses beyond 1 000 000
+        unsigned long long lr = 0;
+        for (uint32_t ci = lane; ci < tr.n_combos; ci += 64) {
+            unsigned long long prod = 1;
+            for (uint32_t m = tr.combo_off[ci]; m < tr.combo_off[ci + 1]; m++) prod = min(prod * cnt(tr.combo_ns[m]), kCap);
+            lr = min(lr + prod, kCap);
+        }
+        uint32_t ffm = 0;
+        for (uint32_t j = lane; j < tr.n_pairs; j += 64) ffm += cnt(tr.pair_ns[j]);
+        const uint32_t n_lr = wave_sum((uint32_t)lr) + tr.add_const, n_ffm = wave_sum(ffm);
+        if (n_lr > 1000000u || n_ffm > 1000000u) return kTextNeedsHost;
+        facts->n_lr = n_lr;
+        facts->n_ffm = n_ffm;
+        if (CAND) {
+            const TextCandidate &cd = a.cand;
+            auto covered = [&](uint32_t nsi) { return nsi < cd.n_cover_slots && ((cd.cover[nsi >> 5] >> (nsi & 31u)) & 1u) != 0; };
+            bool bad = false;
+            for (uint32_t j = lane; j < cd.n_cover_slots; j += 64) bad = bad || (covered(j) && L.slots[j] != kNoFeatures);
+            for (uint32_t j = lane; j < tr.n_pairs; j += 64) {
+                const uint32_t nsi = tr.pair_ns[j], fk = tr.pair_fk[j];
+                if (covered(nsi)) continue;
+                const uint32_t w = L.slots[nsi];
+                if ((w & kNotSingle) == 0) {
+                    bad = bad || present_dev(cd, w & tr.ffm_mask, fk);
+                } else if (w != kNoFeatures) {  // the run's feature tokens are the range's features, in order
+                    for (uint32_t t = L.slot_run[nsi]; t < ntok && L.tok_kind[t] != 0; t++) bad = bad || present_dev(cd, L.tok_a[t] & tr.ffm_mask, fk);
+                }
+            }
+            facts->record_ok = __ballot(bad) == 0ull;
+        }
+    }
+    if (WRITE) {
         if (lane == 0) {
             dst[0] = len;
-            dst[1] = label;
-            dst[2] = imp;
+            dst[1] = a.set_word1 ? a.word1 : CAND ? a.cand.ctx_rec[1] : label;
+            dst[2] = CAND ? a.cand.ctx_rec[2] : imp;
         }
         for (uint32_t j = lane; j < nns; j += 64) dst[kHeaderLen + j] = L.slots[j];
     }
@@ -272,22 +355,29 @@ __device__ inline LineLds carve(unsigned char *p) {
     p += 4 * kTextMaxNamespaces;
     L.tok_start = reinterpret_cast<uint16_t *>(p);
     p += 2 * TOKCAP;
+    L.slot_run = reinterpret_cast<uint16_t *>(p);
+    p += 2 * kTextMaxNamespaces;
     L.tok_kind = p;
     return L;
 }
 template <int STAGE, int TOKCAP>
 constexpr int lds_bytes() {
-    return STAGE + 32 + 11 * TOKCAP + 4 * kTextMaxNamespaces;
+    return STAGE + 32 + 11 * TOKCAP + 6 * kTextMaxNamespaces;
 }
 
 // WRITE: does this line's record get written, and where
 __device__ inline bool write_target(const TextParseArgs &a, uint32_t line, uint32_t **dst) {
-    if (line >= a.n_used || a.status[line].x != kTextDeviceOk) return false;
+    if (line >= a.n_used || (a.status[line].x & 0xffu) != kTextDeviceOk) return false;
     *dst = a.dst + a.dst_off[line];
     return true;
 }
 
-template <bool WRITE>
+__device__ inline uint4 status_word(uint32_t status, const LineFacts &f) {
+    if (status != kTextDeviceOk) return make_uint4(status, 0u, 0u, 0u);
+    return make_uint4(status | (f.record_ok ? kTextRecordOk : 0u), f.len, f.n_lr, f.n_ffm);
+}
+
+template <bool WRITE, bool CAND>
 __global__ __launch_bounds__(64 * kShortWaves) void text_parse_short(TextParseArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kShortWaves][lds_bytes<kShortStage, kShortTok>()];
     static_assert(lds_bytes<kShortStage, kShortTok>() % 16 == 0, "wave images stay 16-byte aligned");
@@ -297,18 +387,19 @@ __global__ __launch_bounds__(64 * kShortWaves) void text_parse_short(TextParseAr
     const uint32_t start = a.lstart[line], size = a.lstart[line + 1] - start;
     uint32_t *dst = nullptr;
     if (WRITE && !write_target(a, line, &dst)) return;
-    uint32_t status = kTextNeedsHost, len = 0;
+    uint32_t status = kTextNeedsHost;
+    LineFacts facts;
     if (ns_ok(a.ns) && size >= 1 && size <= (uint32_t)kLongStage) {
         if (size > (uint32_t)kShortStage) {  // for the single-wave workgroups
             if (lane == 0) a.long_list[atomicAdd(a.long_count, 1u)] = line;
             return;
         }
-        status = parse_line_wave<kShortTok, WRITE>(a, start, size, carve<kShortStage, kShortTok>(lds[wave]), dst, &len);
+        status = parse_line_wave<kShortTok, WRITE, CAND>(a, start, size, carve<kShortStage, kShortTok>(lds[wave]), dst, &facts);
     }
-    if (!WRITE && lane == 0) a.status[line] = make_uint2(status, status == kTextDeviceOk ? len : 0u);
+    if (!WRITE && lane == 0) a.status[line] = status_word(status, facts);
 }
 
-template <bool WRITE>
+template <bool WRITE, bool CAND>
 __global__ __launch_bounds__(64) void text_parse_long(TextParseArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[lds_bytes<kLongStage, kLongTok>()];
     const uint32_t lane = threadIdx.x & 63u;
@@ -318,9 +409,9 @@ __global__ __launch_bounds__(64) void text_parse_long(TextParseArgs a) {
         const uint32_t start = a.lstart[line], size = a.lstart[line + 1] - start;
         uint32_t *dst = nullptr;
         if (WRITE && !write_target(a, line, &dst)) continue;
-        uint32_t len = 0;
-        const uint32_t status = parse_line_wave<kLongTok, WRITE>(a, start, size, carve<kLongStage, kLongTok>(lds), dst, &len);
-        if (!WRITE && lane == 0) a.status[line] = make_uint2(status, status == kTextDeviceOk ? len : 0u);
+        LineFacts facts;
+        const uint32_t status = parse_line_wave<kLongTok, WRITE, CAND>(a, start, size, carve<kLongStage, kLongTok>(lds), dst, &facts);
+        if (!WRITE && lane == 0) a.status[line] = status_word(status, facts);
         wave_sync();  // the next line reuses the image
     }
 }
@@ -382,12 +473,19 @@ hipError_t text_parse_launch(const TextParseArgs &a, bool write, hipStream_t str
     hipError_t e = hipMemsetAsync(a.long_count, 0, 4, stream);
     if (e != hipSuccess) return e;
     const uint32_t grid = (a.nlines + kShortWaves - 1) / kShortWaves;
-    if (write) {
-        text_parse_short<true><<<grid, 64 * kShortWaves, 0, stream>>>(a);
-        text_parse_long<true><<<256, 64, 0, stream>>>(a);
+    const bool cand = a.cand.ctx_rec != nullptr;
+    if (write && cand) {
+        text_parse_short<true, true><<<grid, 64 * kShortWaves, 0, stream>>>(a);
+        text_parse_long<true, true><<<256, 64, 0, stream>>>(a);
+    } else if (write) {
+        text_parse_short<true, false><<<grid, 64 * kShortWaves, 0, stream>>>(a);
+        text_parse_long<true, false><<<256, 64, 0, stream>>>(a);
+    } else if (cand) {
+        text_parse_short<false, true><<<grid, 64 * kShortWaves, 0, stream>>>(a);
+        text_parse_long<false, true><<<256, 64, 0, stream>>>(a);
     } else {
-        text_parse_short<false><<<grid, 64 * kShortWaves, 0, stream>>>(a);
-        text_parse_long<false><<<256, 64, 0, stream>>>(a);
+        text_parse_short<false, false><<<grid, 64 * kShortWaves, 0, stream>>>(a);
+        text_parse_long<false, false><<<256, 64, 0, stream>>>(a);
     }
     return hipGetLastError();
 }

@@ -158,6 +158,20 @@ class DeviceVowpalParser:
                                                    max_records, C.byref(nr), C.byref(nw), C.byref(used))
         return words[: nw.value].copy(), off[: nr.value + 1].copy(), used.value, rc
 
+    def parse_candidates(self, prefix: "ParsePrefix", cache, fbt, text: bytes, max_lines=None, words_cap=None):
+        """Every line of `text` as a candidate of the context `prefix` scanned and `cache` (a BlockCache that went through cover_record)
+        holds: VowpalParser.next_vowpal_candidate line by line, lines that start with '|' scanned by the device.  -> (records u32[],
+        rec_off u64[n + 1], info: an array of capi.CANDIDATE_INFO per line -- code, is_delta, record_ok, by_host, n_lr, n_ffm)"""
+        max_lines = text.count(b"\n") + 1 if max_lines is None else max_lines
+        words_cap = (len(text) + 64) * 2 + 64 * 1024 if words_cap is None else words_cap
+        words = np.empty(max(words_cap, 1), dtype=np.uint32)
+        off = np.zeros(max_lines + 1, dtype=np.uint64)
+        info = np.zeros(max(max_lines, 1), dtype=capi.CANDIDATE_INFO)
+        nl, nw = C.c_uint64(), C.c_uint64()
+        capi.check(self.L.fwgpu_text_parser_parse_candidates(self.h, prefix.h, cache.h, C.byref(fbt.c), text, len(text), max_lines,
+                                                             capi.ptr(words), words_cap, capi.ptr(off), capi.ptr(info), C.byref(nl), C.byref(nw)))
+        return words[: nw.value].copy(), off[: nl.value + 1].copy(), info[: nl.value].copy()
+
     def last_lines(self):
         """(lines the last call took, lines of those the host parsed)"""
         n, h = C.c_uint64(), C.c_uint64()

@@ -220,6 +220,17 @@ class BlockCache:
         check(capi.lib().fwgpu_block_cache_filter(self.h, ptr(ffm), len(ffm), ptr(out), C.byref(n)))
         return out[: n.value]
 
+    def cover_record(self, translator, record):
+        """`record` is the context's own record: the namespace slots it fills are covered, and record batches of its requests can start from
+        this cache (fwgpu_block_cache_cover_record)"""
+        r = np.ascontiguousarray(record, dtype=np.uint32)
+        check(capi.lib().fwgpu_block_cache_cover_record(self.h, C.byref(translator.c), ptr(r), len(r)))
+
+    def record_ok(self, translator, record) -> bool:
+        """does leaving out the covered slots of this request's (merged) record equal filtering its translation (fwgpu_block_cache_record_ok)"""
+        r = np.ascontiguousarray(record, dtype=np.uint32)
+        return bool(capi.lib().fwgpu_block_cache_record_ok(self.h, C.byref(translator.c), ptr(r), len(r)))
+
     def close(self):
         if self.h:
             capi.lib().fwgpu_block_cache_free(self.h)

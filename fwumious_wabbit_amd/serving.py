@@ -21,6 +21,10 @@ def _lib():
         L.free_predictor.restype = None
         L.fwgpu_predictor_predict_batch.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_void_p]
         L.fwgpu_predictor_predict_batch.restype = C.c_int
+        L.fwgpu_predictor_predict_text.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.fwgpu_predictor_predict_text.restype = C.c_int
+        L.fwgpu_predictor_last_text_route.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.fwgpu_predictor_last_text_route.restype = C.c_int
         L._fw_ffi_ready = True
     return L
 
@@ -55,6 +59,21 @@ class Predictor:
         out = np.zeros(len(arr), dtype=np.float32)
         capi.check(self.L.fwgpu_predictor_predict_batch(self.p, arr, len(arr), int(with_cache), capi.ptr(out)))
         return out
+
+    def predict_text(self, text: bytes, with_cache=False, cap=None) -> np.ndarray:
+        """a request as one text, a candidate per line, scanned on the device: what predict_batch returns for the lines (each with its
+        newline); with a device cache the lines never become records on the host (fwgpu_predictor_predict_text)"""
+        cap = text.count(b"\n") + 1 if cap is None else cap
+        out = np.zeros(max(cap, 1), dtype=np.float32)
+        n = C.c_uint64()
+        capi.check(self.L.fwgpu_predictor_predict_text(self.p, text, len(text), int(with_cache), capi.ptr(out), cap, C.byref(n)))
+        return out[: n.value]
+
+    def last_text_route(self):
+        """(lines of the last predict_text, lines of those the host parsed, whether the call went through predict_batch)"""
+        n, h, f = C.c_uint64(), C.c_uint64(), C.c_int()
+        capi.check(self.L.fwgpu_predictor_last_text_route(self.p, C.byref(n), C.byref(h), C.byref(f)))
+        return n.value, h.value, bool(f.value)
 
     def close(self):
         if self.p:

@@ -35,6 +35,17 @@ void free_predictor(FfiPredictor *ptr);
  * (with_cache == 0) or fw_predict_with_cache (with_cache != 0) would be given, out[i] what it would return. */
 int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, uint32_t n, int with_cache, float *out);
 
+/* The same request as ONE text, a candidate per line (a last line may lack its newline), scanned by the device: out[i] is what
+ * fw_predict_with_cache (with_cache != 0) or fw_predict would return for line i with its newline, -1.0 for a line that does not
+ * parse or gives no record; *n = number of lines; FWGPU_ERR_RANGE when cap is smaller.  With a device cache whose context is its
+ * own record, lines that start with '|' never reach the host parser and the records go from the parser's write pass into the
+ * launch.  A request in which a candidate names a cached namespace with another feature, repeats a cached feature in an uncached
+ * namespace or continues the context's last namespace takes fwgpu_predictor_predict_batch on the split lines, as do predictors
+ * without a device cache (--packed_weights) and FWGPU_SERVING_HOST_PARSE=1: same numbers.  fwgpu_predictor_last_text_route: lines
+ * of the last call on this predictor, how many of them the host parsed, and whether the call went through predict_batch. */
+int fwgpu_predictor_predict_text(FfiPredictor *p, const char *text, uint64_t len, int with_cache, float *out, uint64_t cap, uint64_t *n);
+int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint64_t *host_lines, int *fell_back);
+
 #ifdef __cplusplus
 }
 #endif

@@ -569,6 +569,25 @@ int fwgpu_text_parser_parse_buffer(fwgpu_text_parser *tp, const char *text, uint
                                    uint64_t *consumed);
 int fwgpu_text_parser_last_lines(const fwgpu_text_parser *tp, uint64_t *lines, uint64_t *host_lines);
 const char *fwgpu_text_parser_command_argument(const fwgpu_text_parser *tp);
+/* Every line of `text` as one candidate of a context: fwgpu_parser_parse_candidate(px, line) line by line, no line stops the walk.
+ * `cache` is the context's cache (it went through fwgpu_block_cache_cover_record) and `px` the scan of the same context whose output is
+ * that record (fwgpu_parse_prefix_is_record); anything else, or a parser on another device, is FWGPU_ERR_INVALID.  A line that starts
+ * with '|' is scanned by the device: its candidate-only record is its stand-alone record with the context record's words 1 and 2 and
+ * NO_FEATURES in every slot whose merged form equals the context's slot word.  Every other line (a feature token that goes on in the
+ * context's last namespace, a label, an empty line, what the kernel leaves to the host in any mode) goes through
+ * fwgpu_parser_parse_candidate.  Per line: code = that function's return code, rec_off[i] .. rec_off[i + 1] = its record in `words` (no
+ * words for an error or an empty record), is_delta, n_lr / n_ffm = the entry counts of its translation on top of the context's record,
+ * record_ok = fwgpu_block_cache_record_ok for the record in the form it has (0 when the record does not count), by_host = 1 when the
+ * host parsed it.  FWGPU_ERR_RANGE: more than max_lines lines or more than words_cap words. */
+typedef struct fwgpu_candidate_info {
+    int32_t code;
+    uint8_t is_delta, record_ok, by_host, pad;
+    uint32_t n_lr, n_ffm;
+} fwgpu_candidate_info;
+int fwgpu_text_parser_parse_candidates(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache,
+                                       const struct fwgpu_translator_config *t, const char *text, uint64_t len, uint64_t max_lines,
+                                       uint32_t *words, uint64_t words_cap, uint64_t *rec_off, fwgpu_candidate_info *info,
+                                       uint64_t *n_lines, uint64_t *n_words);
 /* Text -> raw-record batch, as fwgpu_record_batch_create makes from the same records; the records the device parsed never leave
  * it.  Stops as fwgpu_parser_parse_buffer stops (max_records, a line that is not an example): the batch holds the examples before
  * the stop and *consumed says where to go on.  A call whose FIRST line is not an example returns that line's code (FWGPU_PARSE_FLUSH,
