@@ -531,3 +531,96 @@ hipError_t sparse_apply(const SparseApplyArgs &a, int optimizer, hipStream_t str
 }
 
 }  // namespace fwgpu
+
+// ------------------------------------------------------------------ debug entry points (tests/test_gpu_sparse_kernels.py)
+// sparse_reduce / sparse_apply on device pointers the caller owns, with the scratch buffers allocated here: nothing but the
+// argument structs is filled in, the kernels are the ones the multi-GPU step launches.
+namespace {
+struct DevScratch {  // device allocations of one debug call, freed when it returns
+    void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int n = 0;
+    hipError_t get(void **out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 4);
+        if (e == hipSuccess) p[n++] = *out;
+        return e;
+    }
+    ~DevScratch() {
+        for (int i = 0; i < n; i++) (void)hipFree(p[i]);
+    }
+};
+}  // namespace
+
+extern "C" int fwgpu_debug_sparse_reduce(const void *keys, uint32_t n, int key_bits, const void *desc, uint32_t max_entries, uint32_t R, uint32_t k,
+                                         const float *split, uint32_t split_len, const float *selfw, uint32_t selfw_stride, const float *gbuf,
+                                         uint32_t *bk_key, float *bk_rows, uint32_t *count, void *stream) {
+    using namespace fwgpu;
+    if (!keys || !desc || !gbuf || !bk_key || !bk_rows || !count || (R && (!split || !selfw)))
+        return fail(FWGPU_ERR_INVALID, "debug_sparse_reduce: null pointer");
+    if (!max_entries || key_bits < 33 || key_bits > 64 || (R && !k) || (R && R % k)) return fail(FWGPU_ERR_INVALID, "debug_sparse_reduce: bad shape (R % k, max_entries, key_bits)");
+    hipStream_t st = (hipStream_t)stream;
+    DevScratch mem;
+    SparseReduceArgs a{};
+    a.keys = (const unsigned long long *)keys;
+    a.n = n;
+    a.key_bits = key_bits;
+    a.desc = (const uint2 *)desc;
+    a.max_entries = max_entries;
+    a.tmp_bytes = sparse_tmp_bytes(std::max<uint32_t>(n, 1));
+    FWGPU_HIP(mem.get((void **)&a.keys_sorted, (size_t)n * 8));
+    FWGPU_HIP(mem.get((void **)&a.flags, ((size_t)n + 1) * 4));
+    FWGPU_HIP(mem.get((void **)&a.pos, ((size_t)n + 1) * 4));
+    FWGPU_HIP(mem.get(&a.tmp, a.tmp_bytes));
+    FWGPU_HIP(mem.get((void **)&a.d_count, 4));
+    a.R = R;
+    a.k = k;
+    a.split = split;
+    a.split_len = split_len;
+    a.selfw = selfw;
+    a.selfw_stride = selfw_stride;
+    a.gbuf = gbuf;
+    a.bk_key = bk_key;
+    a.bk_rows = bk_rows;
+    hipError_t e = sparse_reduce(a, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, a.d_count, 4, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);  // (also before the scratch buffers go)
+    FWGPU_HIP(e);
+    FWGPU_HIP(es);
+    return FWGPU_OK;
+}
+
+extern "C" int fwgpu_debug_sparse_apply(const uint32_t *all_key, const float *all_rows, const uint32_t *counts, uint32_t n_ranks, uint32_t stride, int key_bits,
+                                        uint32_t R, uint32_t k4, float *w, float *acc, int optimizer, float rate, float minus_power_t, const float *lut,
+                                        void *stream) {
+    using namespace fwgpu;
+    if (!all_key || !all_rows || !counts || !w || !lut || (R && !acc)) return fail(FWGPU_ERR_INVALID, "debug_sparse_apply: null pointer");
+    if (key_bits < 33 || key_bits > 64 || (k4 && R % 4) || (uint64_t)n_ranks * stride >= 0xffffffffull)
+        return fail(FWGPU_ERR_INVALID, "debug_sparse_apply: bad shape (k4 with R % 4, key_bits, n_ranks * stride)");
+    if (optimizer != FWGPU_OPT_SGD && optimizer != FWGPU_OPT_ADAGRAD_FLEX && optimizer != FWGPU_OPT_ADAGRAD_LUT)
+        return fail(FWGPU_ERR_INVALID, "debug_sparse_apply: unknown optimizer");
+    hipStream_t st = (hipStream_t)stream;
+    DevScratch mem;
+    const uint32_t n = n_ranks * stride;
+    SparseApplyArgs a{};
+    a.all_key = all_key;
+    a.all_rows = all_rows;
+    a.counts = counts;
+    a.n_ranks = n_ranks;
+    a.stride = stride;
+    a.key_bits = key_bits;
+    a.tmp_bytes = sparse_tmp_bytes(std::max<uint32_t>(n, 1));
+    FWGPU_HIP(mem.get((void **)&a.keys, (size_t)n * 8));
+    FWGPU_HIP(mem.get((void **)&a.keys_sorted, (size_t)n * 8));
+    FWGPU_HIP(mem.get(&a.tmp, a.tmp_bytes));
+    a.R = R;
+    a.k4 = k4 != 0;
+    a.w = w;
+    a.acc = acc;
+    a.rate = rate;
+    a.minus_power_t = minus_power_t;
+    a.lut = lut;
+    const hipError_t e = sparse_apply(a, optimizer, st);
+    const hipError_t es = hipStreamSynchronize(st);  // (the scratch buffers go when this returns)
+    FWGPU_HIP(e);
+    FWGPU_HIP(es);
+    return FWGPU_OK;
+}

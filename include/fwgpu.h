@@ -500,6 +500,22 @@ int fwgpu_debug_coherence_probe(int device, int use_sc1, uint32_t iters, uint32_
  * otherwise the split-K kernel runs where K % 8 == 0 and the operands allow 16-byte loads.  The three (ta, tb) pairs the head uses: (0, 1), (1, 0), (0, 0). */
 int fwgpu_debug_head_gemm(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc, int ta, int tb, int epilogue,
                           const float *bias, float *aux, int relu, int tiled, void *stream);
+/* The reduce and apply steps of the row-sparse gradient buckets (sparse.hip) on device pointers, for tests against a plain f32 restatement
+ * (tests/sparse_ref.py): the calls only fill the argument structs of the multi-GPU step, allocate its scratch buffers and wait for the stream.
+ * reduce: keys[n] = (hash << 32 | slot) or ~0 (padding) in any order, key_bits = 32 + bits of the largest hash; desc[slot] = {value bits, field};
+ *   slot = example * max_entries + entry.  R != 0 (FFM): split[example * split_len + field * R + e], selfw[example * selfw_stride + entry * k + e % k],
+ *   gbuf[example]; the 16-byte kernel runs where k % 4 == 0 and split_len % 4 == 0 (split, bk_rows 16-byte aligned).  R == 0 (LR): one float per bucket
+ *   row, split / selfw unused.  Out: bk_key[rows], bk_rows[rows * max(R, 1)] on the device, *count = rows on the host.
+ * apply: all_key / all_rows hold n_ranks * stride bucket rows of which rank r's first counts[r] (device) are valid; one rank's keys must be sorted by
+ *   (hash, index).  R != 0: tables w / acc, k4 != 0 = the 16-byte kernel (R % 4 == 0; w, acc, all_rows and every hash on 16-byte boundaries);
+ *   R == 0: w = the {w, acc} pair table, acc unused.  lut: 2048 floats on the device.
+ * FWGPU_ERR_INVALID: a null pointer, k == 0 with R != 0, R % k != 0, k4 with R % 4 != 0.  Alignment and table bounds are the caller's. */
+int fwgpu_debug_sparse_reduce(const void *keys, uint32_t n, int key_bits, const void *desc, uint32_t max_entries, uint32_t R, uint32_t k,
+                              const float *split, uint32_t split_len, const float *selfw, uint32_t selfw_stride, const float *gbuf, uint32_t *bk_key,
+                              float *bk_rows, uint32_t *count, void *stream);
+int fwgpu_debug_sparse_apply(const uint32_t *all_key, const float *all_rows, const uint32_t *counts, uint32_t n_ranks, uint32_t stride, int key_bits,
+                             uint32_t R, uint32_t k4, float *w, float *acc, int optimizer, float rate, float minus_power_t, const float *lut,
+                             void *stream);
 
 /* ---------------------------------------------------------------- feed path: namespace map, VW text parser, input cache
  * (SURVEY.md 8 f1/f3).  Host-side code; none of it needs a device.

@@ -349,7 +349,7 @@ def test_dist_symbols_are_exported_without_loading_rccl():
     for name in ("fwgpu_dist_unique_id", "fwgpu_dist_init", "fwgpu_dist_learn_sharded", "fwgpu_dist_gather_tables",
                  "fwgpu_dist_all_reduce_sum", "fwgpu_dist_group_create", "fwgpu_dist_group_learn_sharded",
                  "fwgpu_dist_learn_sparse", "fwgpu_dist_learn_sparse_batch", "fwgpu_dist_group_learn_sparse",
-                 "fwgpu_learn_batch_sync", "fwgpu_split_create"):
+                 "fwgpu_learn_batch_sync", "fwgpu_split_create", "fwgpu_debug_sparse_reduce", "fwgpu_debug_sparse_apply"):
         assert hasattr(L, name)
     with open("/proc/self/maps") as f:
         assert "librccl" not in f.read() or "torch" in open("/proc/self/maps").read()

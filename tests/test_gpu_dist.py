@@ -208,15 +208,17 @@ def _run_sparse(n_ranks, mi, recs, off, per_rank, n_steps):
     (10, 4, 14, 14, 0.0, 3000, fw.Optimizer.AdagradLUT),     # tiny tables: most rows overlap a neighbour, hot rows span several 64-blocks
     (30, 8, 16, 18, 3.0, 50000, fw.Optimizer.AdagradLUT),    # config C's shape
     (12, 2, 15, 15, 1.0, 5000, fw.Optimizer.AdagradFlex),
-    (8, 4, 14, 14, 0.0, 2000, fw.Optimizer.SGD)])
+    (8, 4, 14, 14, 0.0, 2000, fw.Optimizer.SGD),
+    (30, 16, 16, 20, 3.0, 50000, fw.Optimizer.AdagradLUT),   # config E's FFM geometry (R = 480: the second pass of the 256-float loops), 16-byte kernels, t_global phase kernels
+    (28, 10, 15, 18, 1.0, 20000, fw.Optimizer.AdagradLUT)])  # R = 280 on the scalar kernels; field 25 holds floats 250..259, on both sides of float 256
 def test_sparse_bucket_step_matches_the_oracle(n_ns, k, bits, ffm_bits, extra, ids, opt):
     """Row-sparse gradient buckets (fwgpu_dist_group_learn_sparse) on 1, 2 and 3 ranks (uneven micro-batches) == the oracle's
     fwo_learn_sparse with the same partition: predictions and all three tables to f32 rounding; the replicas of a job bit-identical."""
     mi, ocfg, ots = make_pair(n_ns, k, bits, ffm_bits, opt, lr=0.05, ffm_lr=0.05)
-    steps, gb = 5, 200
+    steps, gb = (3, 120) if k == 16 else (5, 200)  # (the oracle's k = 16 model is the slow part of that row)
     recs, off = fw.synth_records(n_ns, extra, 1.1, ids, 0.1, 83, 0, steps * gb)
     y = record_labels(recs, off)
-    for parts in ([gb], [gb // 2, gb // 2], [90, 70, 40]):
+    for parts in ([gb], [gb // 2, gb // 2], [gb * 9 // 20, gb * 7 // 20, gb * 4 // 20]):  # (200: 90, 70, 40)
         om = fwo.Model(ocfg)
         pe = np.cumsum(parts)
         p_ref = np.concatenate([om.learn_sparse(ots, recs[int(off[s * gb]):int(off[(s + 1) * gb])], off[s * gb:(s + 1) * gb + 1] - off[s * gb], pe)
@@ -230,6 +232,7 @@ def test_sparse_bucket_step_matches_the_oracle(n_ns, k, bits, ffm_bits, extra, i
                 # the general gradients differ from the oracle's in the last bits (the forward sums are taken in another order),
                 # so the tables agree to f32 rounding, plus the odd AdagradLUT bucket edge (see `close` above)
                 bad = np.abs(a - b) > 3e-5 + 1e-5 * np.abs(b)
+                print(f"sparse step F={n_ns} k={k} parts={parts} table {t}: {int(bad.sum())} of {a.size} entries outside the tolerance, largest difference {float(np.abs(a - b).max()):.3e}")
                 assert int(bad.sum()) <= max(3, a.size // 10000) and float(np.abs(a - b).max()) < 5e-3, (parts, t, int(bad.sum()), float(np.abs(a - b).max()))
                 # ... but the replicas of one job are the same bits: every rank applied the same buckets in the same order
                 assert np.array_equal(a, np.asarray(tables[0][t])), (parts, t)
