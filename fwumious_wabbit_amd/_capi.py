@@ -204,6 +204,7 @@ def lib():
         "fwgpu_debug_head_inputs": [vp, vp, u64],
         "fwgpu_debug_coherence_probe": [i32, i32, u32, P(u32), P(u32)],
         "fwgpu_debug_head_gemm": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp],
+        "fwgpu_debug_head_step": [vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, P(f32), vp],
         "fwgpu_debug_sparse_reduce": [vp, u32, i32, vp, u32, u32, u32, vp, u32, vp, u32, vp, vp, vp, P(u32), vp],
         "fwgpu_debug_sparse_apply": [vp, vp, vp, u32, u32, i32, u32, u32, vp, vp, i32, f32, f32, vp, vp],
         "fwgpu_synth_records": [P(SynthConfig), u64, u32, vp, u64, vp, P(u64)],

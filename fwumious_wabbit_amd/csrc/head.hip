@@ -224,10 +224,21 @@ static hipError_t gemm(const float *A, const float *B, float *C, int M, int N, i
 // One wave per example: logit = w_f . [h_last | x] + b_f (regressor.rs:307-319), sigmoid / log-loss gradient
 // (block_loss_functions.rs:105-153); then the final neuron's input gradients from the FROZEN w_f: d h_last (times the last
 // ReLU mask) and the direct part of dx.
-__global__ void __launch_bounds__(256) head_final_kernel(const float *__restrict__ h_last, const float *__restrict__ mask_last, const float *__restrict__ x,
+//
+// An example whose general gradient is 0 (importance 0, a NaN logit, a logit beyond +-50, or p == label to the last bit) learns nothing: the oracle's micro-batch mode leaves
+// it out of every dense gradient sum.  Its dz rows are zeros here, but the gradient products and column sums still multiply them by the example's rows of x and h, and a
+// logit is NaN or saturated exactly when those rows may hold an inf or a NaN: 0 * inf = NaN in dW, and every dense weight the sum feeds is lost.  So, the forward done,
+// the example's wave overwrites its rows of x and of every layer's h with zeros (x is a micro-batch's own buffer that nothing reads after the head step): no test inside
+// the products' inner loops.
+struct HeadRows {
+    float *h[kNnMaxLayers];
+    int w[kNnMaxLayers];
+    int n_layers;
+};
+__global__ void __launch_bounds__(256) head_final_kernel(const float *h_last, const float *__restrict__ mask_last, float *x,
                                                          const float *__restrict__ wf, const float *__restrict__ yi, float *__restrict__ pred,
                                                          float *__restrict__ gvec, float *__restrict__ dz_last, float *__restrict__ dx, int n, int wl,
-                                                         int X, int topo_one, int update) {
+                                                         int X, int topo_one, int update, HeadRows rows) {
     const int lane = threadIdx.x & 63;
     const int ex = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ex >= n) return;
@@ -262,6 +273,11 @@ __global__ void __launch_bounds__(256) head_final_kernel(const float *__restrict
     if (!update) return;  // (a predict-only batch has no gradient buffers)
     for (int i = lane; i < wl; i += 64) dz_last[(size_t)ex * wl + i] = g * wf[i] * mask_last[(size_t)ex * wl + i];
     for (int i = lane; i < X; i += 64) dx[(size_t)ex * X + i] = topo_one ? g * wf[wl + i] : 0.0f;
+    if (g == 0.0f) {  // (wave-uniform; the wave's reads of these rows ended with the reduction above)
+        for (int i = lane; i < X; i += 64) x[(size_t)ex * X + i] = 0.0f;
+        for (int l = 0; l < rows.n_layers; ++l)
+            for (int i = lane; i < rows.w[l]; i += 64) rows.h[l][(size_t)ex * rows.w[l] + i] = 0.0f;
+    }
 }
 
 // out[c] = sum_e scale[e] * Mat[e, c]  (scale == NULL: plain column sums): the bias gradients and the final neuron's weight
@@ -374,7 +390,7 @@ int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, f
         hs.n_cap = n;
     }
     if (!hs.dw) FWGPU_HIP(hipMalloc((void **)&hs.dw, (size_t)r->nn_len * sizeof(float)));
-    const float *x = sp->d_x + (size_t)first * X;
+    float *x = sp->d_x + (size_t)first * X;  // (a training step zeroes the rows of examples that learn nothing: head_final_kernel)
     const float *yi = sp->d_g + 2 * (size_t)first;
     float *dx = sp->d_dx + (size_t)first * X;
     // ---- forward through the hidden layers: z = in . W^T + b, ReLU (or identity) with its mask
@@ -390,8 +406,14 @@ int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, f
     // ---- final neuron, sigmoid, gradient; input gradients of the final neuron
     const uint32_t wl = nn.out[L - 1];
     const float *wf = nn.w + nn.off[L];
+    HeadRows rows{};
+    rows.n_layers = (int)L;
+    for (uint32_t l = 0; l < L; l++) {
+        rows.h[l] = hs.h[l];
+        rows.w[l] = (int)nn.out[l];
+    }
     hipLaunchKernelGGL(head_final_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, hs.h[L - 1], hs.m[L - 1], x, wf, yi, d_pred, hs.gvec,
-                       hs.dz[L - 1], dx, (int)n, (int)wl, (int)X, nn.topology == 1 ? 1 : 0, update ? 1 : 0);
+                       hs.dz[L - 1], dx, (int)n, (int)wl, (int)X, nn.topology == 1 ? 1 : 0, update ? 1 : 0, rows);
     FWGPU_HIP(hipGetLastError());
     if (!update) return FWGPU_OK;
     float *dW = hs.dw;
@@ -445,4 +467,57 @@ extern "C" int fwgpu_debug_head_gemm(const float *A, const float *B, float *C, i
     g_force_tiled = false;
     if (e != hipSuccess) return fail(FWGPU_ERR_INVALID, "head_gemm: not one of the head's products ((ta, tb, epilogue) = (0,1,1), (1,0,0), (0,0,2), (0,0,3)) or a launch error");
     return FWGPU_OK;
+}
+
+extern "C" int fwgpu_debug_head_step(fwgpu_regressor *r, const float *x, const float *yi, uint32_t n, int update, float *pred, float *gvec, float *dx,
+                                     float *dW, float *h, float *mask, float *dz, float *step_ms, void *stream) {
+    using namespace fwgpu;
+    if (!r || !x || !yi || !n) return fail(FWGPU_ERR_INVALID, "debug_head_step: null pointer or empty batch");
+    if (!r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "debug_head_step: the model has no deep head");
+    hipStream_t st = (hipStream_t)stream;
+    FWGPU_HIP(hipSetDevice(r->device));
+    const DevNN &nn = r->nn;
+    const size_t nx = (size_t)n * nn.X;
+    fwgpu_split view;  // the buffers of a micro-batch that head_step reads and writes: x, {label, importance}, dx
+    float *d_pred = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto done = [&](int code) {
+        for (float *q : {view.d_x, view.d_g, view.d_dx, d_pred})
+            if (q) (void)hipFree(q);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        return code;
+    };
+    view.owner = r;
+    view.n_cap = n;
+    if (hipMalloc((void **)&view.d_x, nx * 4) != hipSuccess || hipMalloc((void **)&view.d_g, (size_t)n * 8) != hipSuccess ||
+        hipMalloc((void **)&view.d_dx, nx * 4) != hipSuccess || hipMalloc((void **)&d_pred, (size_t)n * 4) != hipSuccess ||
+        hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)
+        return done(fail(FWGPU_ERR_DEVICE, "debug_head_step: allocation failed"));
+    if (hipMemcpyAsync(view.d_x, x, nx * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(view.d_g, yi, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess)
+        return done(fail(FWGPU_ERR_DEVICE, "debug_head_step: upload failed"));
+    if (int rc = head_step(r, &view, 0, n, d_pred, update != 0, st)) return done(rc);
+    if (hipEventRecord(ev[1], st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return done(fail(FWGPU_ERR_DEVICE, "debug_head_step: the step failed"));
+    if (step_ms && hipEventElapsedTime(step_ms, ev[0], ev[1]) != hipSuccess) return done(fail(FWGPU_ERR_DEVICE, "debug_head_step: no event time"));
+    const HeadScratch &hs = scratch_of(r);
+    bool ok = true;
+    auto back = [&](float *dst, const float *src, size_t count) {
+        if (dst && count) ok = ok && hipMemcpy(dst, src, count * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    back(pred, d_pred, n);
+    back(gvec, hs.gvec, n);
+    size_t o = 0;
+    for (uint32_t l = 0; l < nn.n_layers; l++) {  // per layer [n, out_l], the layers back to back
+        const size_t cnt = (size_t)n * nn.out[l];
+        back(h ? h + o : nullptr, hs.h[l], cnt);
+        back(mask ? mask + o : nullptr, hs.m[l], cnt);
+        if (update) back(dz ? dz + o : nullptr, hs.dz[l], cnt);
+        o += cnt;
+    }
+    if (update) {
+        back(dx, view.d_dx, nx);
+        back(dW, hs.dw, r->nn_len);
+    }
+    return done(ok ? FWGPU_OK : fail(FWGPU_ERR_DEVICE, "debug_head_step: read-back failed"));
 }

@@ -457,6 +457,34 @@ class Regressor:
         check(self.L.fwgpu_debug_head_inputs(self.h, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
+    def debug_head_step(self, x, yi, update=True, stream=None):
+        """one step of the mini-batched head on host x (n, X) and yi (n, 2) = {label, importance} and the current dense weights
+        (fwgpu_debug_head_step): a dict of the step's buffers -- pred, gvec (n), h, mask (lists, one (n, out_l) array per hidden layer), ms (the
+        step's kernels between two events); with update also dz (like h), dx (n, X) and dW (TABLE_NN_W layout)"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        yi = np.ascontiguousarray(yi, dtype=np.float32)
+        n, X = x.shape
+        widths = [int(d["width"]) for d in self.mi.nn_layers]
+        assert yi.shape == (n, 2) and widths
+        out = dict(pred=np.empty(n, np.float32), gvec=np.empty(n, np.float32), h=np.empty(n * sum(widths), np.float32),
+                   mask=np.empty(n * sum(widths), np.float32))
+        if update:
+            out.update(dz=np.empty(n * sum(widths), np.float32), dx=np.empty((n, X), np.float32),
+                       dW=np.empty(self.table_len(capi.TABLE_NN_W), np.float32))
+        ms = C.c_float(0.0)
+        p = {k: (ptr(out[k]) if k in out else None) for k in ("pred", "gvec", "dx", "dW", "h", "mask", "dz")}
+        check(self.L.fwgpu_debug_head_step(self.h, ptr(x), ptr(yi), n, int(bool(update)), p["pred"], p["gvec"], p["dx"], p["dW"], p["h"], p["mask"],
+                                           p["dz"], C.byref(ms), stream))
+        for k in ("h", "mask", "dz"):
+            if k in out:
+                flat, o = out[k], 0
+                out[k] = []
+                for w in widths:
+                    out[k].append(flat[o:o + n * w].reshape(n, w))
+                    o += n * w
+        out["ms"] = ms.value
+        return out
+
     def set_prefetch(self, on):
         """updating launches copy the next example's record to LDS during the current example (fwgpu_debug_set_option 7; default on)"""
         check(self.L.fwgpu_debug_set_option(self.h, 7, int(bool(on))))

@@ -500,6 +500,15 @@ int fwgpu_debug_coherence_probe(int device, int use_sc1, uint32_t iters, uint32_
  * otherwise the split-K kernel runs where K % 8 == 0 and the operands allow 16-byte loads.  The three (ta, tb) pairs the head uses: (0, 1), (1, 0), (0, 0). */
 int fwgpu_debug_head_gemm(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc, int ta, int tb, int epilogue,
                           const float *bias, float *aux, int relu, int tiled, void *stream);
+/* One training (update != 0) or predict-only step of the mini-batched head (head.hip head_step) on the regressor's current dense weights, for tests
+ * against a float64 reference (tests/head_ref.py head_train64): host x[n * X] and yi[2 n] ({label, importance} pairs) are copied to device buffers of
+ * their own -- allocated as a micro-batch's are, so every product takes the kernel it takes in training -- the step runs, the stream is waited for,
+ * and the step's buffers come back to the host: pred[n], gvec[n] (the general gradients), per layer and back to back h, mask [n * out_l]; with update
+ * also dz (like h), dx[n * X] and dW[nn_len], the gradient sums in TABLE_NN_W layout as the optimizer step saw them.  An example whose general
+ * gradient is 0 learns nothing: its rows of h come back as zeros after a training step.  NULL outputs are skipped; step_ms: the step's kernels
+ * between two events.  The dense weights and accumulators before and after: fwgpu_table_read / fwgpu_table_write on TABLE_NN_W / TABLE_NN_ACC. */
+int fwgpu_debug_head_step(fwgpu_regressor *r, const float *x, const float *yi, uint32_t n, int update, float *pred, float *gvec, float *dx,
+                          float *dW, float *h, float *mask, float *dz, float *step_ms, void *stream);
 /* The reduce and apply steps of the row-sparse gradient buckets (sparse.hip) on device pointers, for tests against a plain f32 restatement
  * (tests/sparse_ref.py): the calls only fill the argument structs of the multi-GPU step, allocate its scratch buffers and wait for the stream.
  * reduce: keys[n] = (hash << 32 | slot) or ~0 (padding) in any order, key_bits = 32 + bits of the largest hash; desc[slot] = {value bits, field};

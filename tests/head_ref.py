@@ -1,5 +1,7 @@
 """A float64 restatement of the deep head's predict-only forward, for the tests of the batched head predict route
-(test_head_predict_ref_cpu.py pins it against the oracle on the CPU; test_gpu_head_predict.py judges the device with it).
+(test_head_predict_ref_cpu.py pins it against the oracle on the CPU; test_gpu_head_predict.py judges the device with it), and of one
+training step of the mini-batched head (head_train64: test_head_train_ref_cpu.py pins it against the oracle's micro-batch mode,
+test_gpu_head_train.py judges the kernels of head.hip with it).
 
 Both rules of the head input come from oracle/fw_oracle.c, not from the kernels:
   * slot c < C: lr_forward -- the sum of w[hash] * value over the LR entries of combo c;
@@ -32,9 +34,26 @@ SHAPES = {
 }
 
 
+# Further heads for the tests of the training step, on shape a's inputs (X = 29): one unit; widths below, at and above the 64-column tiles, the width
+# being the K of the second layer's forward product and of the first layer's input-gradient product
+TRAIN_SHAPES = {
+    "w1": dict(F=6, k=4, inter=[(0, 1)], layers=[(1, "relu")], topo="one"),
+    "w63": dict(F=6, k=4, inter=[(0, 1)], layers=[(63, "relu"), (63, "relu")], topo="one"),
+    "w64": dict(F=6, k=4, inter=[(0, 1)], layers=[(64, "relu"), (64, "relu")], topo="one"),
+    "w65": dict(F=6, k=4, inter=[(0, 1)], layers=[(65, "relu"), (65, "relu")], topo="one"),
+}
+
+
+def shape_of(name):
+    """(X, layers, topo) of a shape of SHAPES / TRAIN_SHAPES"""
+    s = SHAPES.get(name) or TRAIN_SHAPES[name]
+    F = s["F"]
+    return F + len(s["inter"]) + 1 + F * (F + 1) // 2, s["layers"], s["topo"]
+
+
 def build_shape(name, bits=14, optimizer=fw.Optimizer.AdagradLUT):
     """(ModelInstance with the head, oracle config, oracle translator, oracle nn config) of SHAPES[name]"""
-    s = SHAPES[name]
+    s = SHAPES.get(name) or TRAIN_SHAPES[name]
     mi, ocfg, ots = make_pair(s["F"], s["k"], bits, bits, optimizer, interactions=s["inter"])
     layers = [(w, a, "hu") for w, a in s["layers"]]
     mi.nn_layers = [dict(width=w, activation=a, init=i) for w, a, i in layers]
@@ -162,6 +181,172 @@ def head_forward64(x, nn_w, layers, topo):
         zc = np.where(np.isnan(z), 0.0, np.clip(z, -50.0, 50.0))
         p = 1.0 / (1.0 + np.exp(-zc))
     return p, z
+
+
+# One dot product of f32 terms summed in any order, against the same sum in float64: |got - want| <= DOT_REL * sum |a||b| + DOT_ABS
+# (the project's number: test_head_products_match_a_torch_f32_reference)
+DOT_REL, DOT_ABS = 2e-5, 1e-6
+
+
+def dot_bound(sum_abs):
+    return DOT_REL * np.asarray(sum_abs, dtype=np.float64) + DOT_ABS
+
+
+def head_train64(x, yi, nn_w, layers, topo):
+    """One training step of the mini-batched head in float64, by the rules of oracle/fw_oracle.c (fwo_learn_minibatch, sigmoid_block): every example
+    against the same dense weights, the weight gradients summed over the batch.  x [n, X], yi [n, 2] = {label, importance}.
+      * a ReLU unit's mask is 0 where pre < 0 and 1 elsewhere (pre >= 0; a NaN passes, as in the oracle); an identity layer's mask is all ones;
+      * g = -(label - p) * importance; 0 for importance 0, for a NaN logit and beyond +-50;
+      * an example with g == 0 contributes exactly nothing to dW and has dx == 0 -- whatever its x holds, inf and NaN included;
+      * topology one adds the direct g * w_f[wl:] into dx.
+    Returns a dict of float64 arrays: pre / h / mask / dz (lists, one [n, out_l] array per hidden layer), z, p, g [n], dx [n, X] and dW in
+    TABLE_NN_W layout (head_layout); under "sa" the same keys hold, for each element, the sum of the absolute products that formed it in ITS OWN
+    stage (for a stage-wise bound: dot_bound(sa)); under "tol" the bound propagated from x through every stage before it, each stage adding
+    dot_bound of its own sums to what its inputs carry (for a whole-chain comparison on the host inputs alone; it holds where the masks agree)."""
+    x = np.asarray(x, dtype=np.float64)
+    yi = np.asarray(yi, dtype=np.float64).reshape(-1, 2)
+    nn_w = np.asarray(nn_w, dtype=np.float64)
+    n, X = x.shape
+    lay, total = head_layout(X, layers, topo)
+    assert nn_w.size == total and len(yi) == n
+    L = len(layers)
+    Ws = [nn_w[o:o + out * w_in].reshape(out, w_in) for o, out, w_in in lay]
+    bs = [nn_w[o + out * w_in:o + out * w_in + out] for o, out, w_in in lay]
+    ulp = 2.0 ** -23
+    with np.errstate(invalid="ignore", over="ignore"):
+        pre, h, mask, sa_pre, t_h = [], [], [], [], []
+        hin, t_in = x, np.zeros_like(x)
+        for l in range(L):
+            z_l = hin @ Ws[l].T + bs[l]
+            s_l = np.abs(hin) @ np.abs(Ws[l]).T + np.abs(bs[l])
+            m_l = np.where(z_l < 0.0, 0.0, 1.0) if layers[l][1] == "relu" else np.ones_like(z_l)
+            e_l = (dot_bound(s_l) + t_in @ np.abs(Ws[l]).T) * m_l
+            pre.append(z_l), sa_pre.append(s_l), mask.append(m_l), t_h.append(e_l)
+            h.append(np.where(m_l == 0.0, 0.0, z_l))
+            hin, t_in = h[-1], e_l
+        wl = lay[-2][1]
+        wf, bf = Ws[L][0], bs[L][0]
+        fx = np.concatenate([hin, x], axis=1) if topo == "one" else hin
+        t_fx = np.concatenate([t_in, np.zeros_like(x)], axis=1) if topo == "one" else t_in
+        z = fx @ wf + bf
+        sa_z = np.abs(fx) @ np.abs(wf) + abs(bf)
+        t_z = dot_bound(sa_z) + t_fx @ np.abs(wf)
+        sat = np.isnan(z) | (np.abs(z) > 50.0)
+        zc = np.where(np.isnan(z), 0.0, np.clip(z, -50.0, 50.0))
+        p = 1.0 / (1.0 + np.exp(-zc))
+        label, imp = yi[:, 0], yi[:, 1]
+        g = np.where(sat | (imp == 0.0), 0.0, -(label - p) * imp)
+        t_p = 0.25 * t_z + ulp
+        t_g = np.abs(imp) * t_p + ulp * np.abs(g)
+    on = np.flatnonzero(g != 0.0)  # the other examples are left out of every product below: exactly nothing, whatever their rows hold
+    assert np.all(np.isfinite(x[on])), "a finite logit inside +-50 from a non-finite x"
+    go, t_go = g[on], t_g[on]
+    dW, sa_dW, t_dW = np.zeros(total), np.zeros(total), np.zeros(total)
+    dz, sa_dz, t_dz = [None] * L, [None] * L, [None] * L
+    dx, sa_dx, t_dx = np.zeros((n, X)), np.zeros((n, X)), np.zeros((n, X))
+
+    def rows(full, part, width):
+        out = np.zeros((n, width))
+        out[on] = part
+        return out
+
+    # final neuron: dW_f = sum_e g_e [h_last | x]_e, its bias sum_e g_e; d h_last = g w_f[:wl] through the last mask; the direct part of dx
+    o, _, fin = lay[L]
+    fxo, t_fxo = fx[on], t_fx[on]
+    dW[o:o + fin] = go @ fxo
+    sa_dW[o:o + fin] = np.abs(go) @ np.abs(fxo)
+    t_dW[o:o + fin] = dot_bound(sa_dW[o:o + fin]) + t_go @ np.abs(fxo) + np.abs(go) @ t_fxo
+    dW[o + fin], sa_dW[o + fin] = go.sum(), np.abs(go).sum()
+    t_dW[o + fin] = dot_bound(sa_dW[o + fin]) + t_go.sum()
+    d = go[:, None] * wf[None, :wl] * mask[L - 1][on]
+    t_d = (t_go[:, None] * np.abs(wf[None, :wl]) + 2 * ulp * np.abs(go[:, None] * wf[None, :wl])) * mask[L - 1][on]
+    direct = go[:, None] * wf[None, wl:] if topo == "one" else np.zeros((len(on), X))
+    t_direct = t_go[:, None] * np.abs(wf[None, wl:]) + ulp * np.abs(direct) if topo == "one" else np.zeros((len(on), X))
+    s_d = np.abs(d)
+    for l in range(L - 1, -1, -1):
+        dz[l], sa_dz[l], t_dz[l] = rows(n, d, lay[l][1]), rows(n, s_d, lay[l][1]), rows(n, t_d, lay[l][1])
+        o, out, w_in = lay[l]
+        lin = (x if l == 0 else h[l - 1])[on]
+        t_lin = (np.zeros_like(x) if l == 0 else t_h[l - 1])[on]
+        blk = slice(o, o + out * w_in)
+        sa_blk = np.abs(d).T @ np.abs(lin)
+        dW[blk], sa_dW[blk] = (d.T @ lin).reshape(-1), sa_blk.reshape(-1)
+        t_dW[blk] = (dot_bound(sa_blk) + t_d.T @ np.abs(lin) + np.abs(d).T @ t_lin).reshape(-1)
+        bb = slice(o + out * w_in, o + out * w_in + out)
+        dW[bb], sa_dW[bb] = d.sum(axis=0), np.abs(d).sum(axis=0)
+        t_dW[bb] = dot_bound(sa_dW[bb]) + t_d.sum(axis=0)
+        din, s_in = d @ Ws[l], np.abs(d) @ np.abs(Ws[l])
+        t_din = dot_bound(s_in) + t_d @ np.abs(Ws[l])
+        if l > 0:
+            d, s_d, t_d = din * mask[l - 1][on], s_in * mask[l - 1][on], t_din * mask[l - 1][on]
+        else:
+            dx[on], sa_dx[on], t_dx[on] = direct + din, np.abs(direct) + s_in, t_direct + t_din + ulp * np.abs(direct + din)
+    return dict(pre=pre, h=h, mask=mask, z=z, p=p, g=g, dz=dz, dx=dx, dW=dW,
+                sa=dict(pre=sa_pre, h=sa_pre, z=sa_z, dz=sa_dz, dx=sa_dx, dW=sa_dW),
+                tol=dict(h=t_h, z=t_z, p=t_p, g=t_g, dz=t_dz, dx=t_dx, dW=t_dW))
+
+
+RELU_MARGIN = 4.0  # a drawn example is kept if every ReLU unit's |pre64| is above this many forward bounds of its layer
+
+
+def draw_train_case(name, n, seed, conc=0.0):
+    """A seeded batch for one training step of the head of shape `name`, drawn on the host: x = N(0, 1) times a per-slot scale (log-normal), labels 0 / 1,
+    importances 1 / 0.5 / 0 mixed (example e: 0.5 where e % 5 == 3, 0 where e % 7 == 5), dense weights in which every slot of x and every unit matters:
+    first-layer column i and the final neuron's direct weight on x_i are N(0, 1) / (slot scale * sqrt(in)), the other weights N(0, 1) / sqrt(in), biases
+    N(0, 0.5); the final neuron is then scaled so that the largest |logit| over all drawn examples is 4.  `conc` > 0 gives the columns of every
+    layer log-normal importances (sigma = conc, normalised): fewer terms dominate a unit's sum, so that a wide layer's pre-activations are less often
+    within rounding of 0 (K terms of random sign: sum |products| / |sum| grows like sqrt(K)).
+    Examples with a ReLU unit whose |pre64| <= RELU_MARGIN * dot_bound(its sum of absolute products) are rejected -- by the reference alone -- until n
+    are kept: f32 and float64 may legitimately disagree about such a unit's mask.  Returns dict(x, yi, w: float32; ref: head_train64 of exactly these
+    float32 values; drawn, rejected: examples looked at / rejected among them)."""
+    X, layers, topo = shape_of(name)
+    rng = np.random.default_rng(seed)
+    slot = np.exp(rng.normal(0.0, 1.0, X))
+    pool = n + n // 4 + 32
+    xs = (rng.standard_normal((pool, X)) * slot).astype(np.float32)
+    lay, total = head_layout(X, layers, topo)
+    w = np.zeros(total)
+    for li, (o, out, w_in) in enumerate(lay):
+        imp = np.exp(rng.normal(0.0, conc, w_in)) if conc else np.ones(w_in)
+        imp *= np.sqrt(w_in / (imp ** 2).sum())
+        Wl = rng.standard_normal((out, w_in)) * imp / np.sqrt(w_in)
+        if li == 0:
+            Wl /= slot
+        elif li == len(lay) - 1 and topo == "one":
+            Wl[0, w_in - X:] /= slot
+        w[o:o + out * w_in] = Wl.reshape(-1)
+        w[o + out * w_in:o + out * w_in + out] = 0.5 * rng.standard_normal(out)
+    _, z = head_forward64(xs.astype(np.float64), w, layers, topo)
+    o, _, fin = lay[-1]
+    w[o:o + fin + 1] *= 3.999 / np.abs(z).max()  # (inside 4 after the rounding to float32 too)
+    w = w.astype(np.float32)
+    yi_all = np.stack([rng.integers(0, 2, pool), np.ones(pool)], axis=1).astype(np.float32)
+    ref = head_train64(xs, yi_all, w, layers, topo)
+    near = np.zeros(pool, dtype=bool)
+    for l, (_, act) in enumerate(layers):
+        if act == "relu":
+            near |= (np.abs(ref["pre"][l]) <= RELU_MARGIN * dot_bound(ref["sa"]["pre"][l])).any(axis=1)
+    kept = np.flatnonzero(~near)[:n]
+    assert len(kept) == n, "the pool is too small"
+    drawn = int(kept[-1]) + 1
+    x, yi = xs[kept], yi_all[kept]
+    e = np.arange(n)
+    yi[e % 5 == 3, 1] = 0.5
+    yi[e % 7 == 5, 1] = 0.0
+    ref = head_train64(x, yi, w, layers, topo)
+    assert np.abs(ref["z"]).max() <= 4.0
+    return dict(x=x, yi=yi, w=w, ref=ref, drawn=drawn, rejected=drawn - n, layers=layers, topo=topo, X=X)
+
+
+# The batches of test_gpu_head_train.py: (shape, n, seed, conc).  n around the 16 row groups of the column sums, around the 64-row tiles, ragged; on config
+# E's geometry ("c": 193 777 dense weights, beyond one trip of the optimizer step's grid) 64 and 72 take the split-K gradient product, 100 the tiled one.
+# test_head_train_ref_cpu.py checks that every one of them rejects fewer than a tenth of its draws.
+_NS = (1, 15, 16, 17, 63, 64, 65, 72, 100, 128)
+TRAIN_CASES = ([("a", n, 1000 + n, 0.0) for n in _NS] + [("w65", n, (2315 if n == 15 else 2000 + n), 0.0) for n in _NS] +
+               [("d", 72, 3072, 0.0), ("w1", 72, 4072, 0.0), ("w63", 72, 5063, 0.0), ("w64", 72, 5064, 0.0),
+                ("c", 64, 6064, 3.0), ("c", 72, 6072, 3.0), ("c", 100, 6100, 3.0)])
+REGROW_CASES = [("a", 16, 1016, 0.0), ("a", 128, 1128, 0.0), ("a", 17, 1017, 0.0)]  # one regressor: the scratch buffers grow, then serve a smaller batch
+MAX_REJECTED = 0.1
 
 
 def dense_head_weights(x64, layers, topo, seed, z_max=4.0):

@@ -545,6 +545,7 @@ def test_sync_micro_batch_matches_oracle_micro_batch_mode():
     _sync_parity(6, 4, 12, 12, fw.Optimizer.SGD, n=512, mb=64, seed=55, lr=0.05, ffm_lr=0.05)
     _sync_parity(8, 0, 14, 14, fw.Optimizer.AdagradLUT, n=600, mb=50, seed=56, interactions=[(0, 1)])
     _sync_parity(30, 16, 16, 18, fw.Optimizer.AdagradLUT, n=96, mb=32, seed=57, ids=20000, p_weighted=0.1)
+    _sync_parity(10, 4, 14, 14, fw.Optimizer.AdagradLUT, n=150, mb=64, seed=58)  # a ragged last batch of 22
 
 
 def test_mini_batched_deep_head_matches_oracle_micro_batch_mode():
