@@ -243,6 +243,10 @@ def lib():
         "fwgpu_dequantize_ffm_weights": [vp, u64, vp],
         "fwgpu_trainer_digest_cache": [vp, vp, u64, P(u64)],
         "fwgpu_trainer_digest_text": [vp, vp, vp, C.c_char_p, u64, u32, P(u64), P(u64)],
+        "fwgpu_trainer_digest_text_device": [vp, vp, vp, C.c_char_p, u64, P(u64), P(u64)],
+        "fwgpu_trainer_digest_file_device": [vp, vp, vp, C.c_char_p, P(u64)],
+        "fwgpu_text_parser_last_wait_ns": [vp, P(u64)],
+        "fwgpu_debug_text_plan": [vp, u32, u32, u32, u32, vp, vp, P(u32), vp, vp, P(u32), vp],
         "fwgpu_parser_clone": [vp, P(vp)],
         "fwgpu_input_open": [C.c_char_p, P(vp)],
         "fwgpu_input_read": [vp, vp, u64, P(u64)],

@@ -551,6 +551,29 @@ struct TextLines {
 int text_lines_scan(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache, const fwgpu_translator_config *t,
                     const char *text, uint64_t len, uint64_t piece_bytes, bool zero_word1, TextLines *out);
 int text_lines_place(fwgpu_text_parser *tp, uint32_t *d_records);
+// Training from text (text_parser.cpp; driven by trainer.cpp fwgpu_trainer_digest_text_device).  text_train_begin: once per call, the translator's
+// arrays go up for the status pass's entry counts.  text_train_piece: one piece of text (whole lines; more than 16 MiB only as ONE line) is parsed and
+// planned on the device (textparse.hip text_batch_plan) and its records are placed in the parser's buffer set `set` (0 / 1) -- the caller has retired
+// the launches that read that set.  On return everything is enqueued on the parser's stream; the launches wait for it through an event.
+constexpr uint32_t kTextTrainWorkStride = 16;  // words between the work counters of a piece's launches
+struct TextTrainPiece {
+    uint32_t n_lines = 0, n_take = 0;                          // lines of the piece; examples before the first line that is none
+    uint32_t n_learn = 0, n_windows_learn = 0, n_windows = 0;  // launch windows (textparse.h TextPlanShape)
+    uint64_t n_words = 0, consumed = 0;                        // record words placed; bytes of the piece fully digested
+    int stop = FWGPU_OK;                                       // code of the line that ended the take, with the host parser's message
+    std::string stop_msg;
+    const uint64_t *win_stats = nullptr;                       // host, 7 per window: examples, words, max_lr, max_ffm, max_rec, tot_lr, tot_ffm
+    uint32_t *d_records = nullptr;                             // the set's device buffers: records, rec_off[n_take + 1], one prediction per line,
+    uint64_t *d_rec_off = nullptr;                             // one work counter per window (kTextTrainWorkStride apart)
+    float *d_pred = nullptr;
+    uint32_t *d_work = nullptr;
+};
+int text_train_begin(fwgpu_text_parser *tp, const fwgpu_translator_config *t, int device);
+int text_train_piece(fwgpu_text_parser *tp, const char *text, uint64_t len, int set, uint32_t micro_batch, uint32_t learn_before, TextTrainPiece *out);
+hipStream_t text_train_stream(fwgpu_text_parser *tp);
+int text_train_wait(fwgpu_text_parser *tp);  // the host waits for the parser's stream (counted in fwgpu_text_parser_last_wait_ns)
+// does a record batch whose statistics are set hold an example beyond what the fused kernel stages (record_batch_host_copy_if_oversize would keep a host copy)?
+bool record_batch_is_oversize(fwgpu_batch *b);
 // device-resident raw-record batch (translation happens inside the example kernel)
 int record_batch_alloc(fwgpu_regressor *r, const fwgpu_translator_config *t, uint32_t n_cap, uint64_t words_cap,
                        fwgpu_batch **out, bool host_mapped = false);

@@ -156,11 +156,12 @@ int fwgpu_input_read(fwgpu_input *h, char *buf, uint64_t cap, uint64_t *n) {
 
 void fwgpu_input_close(fwgpu_input *h) { delete h; }
 
-// main.rs:213-270 over an input FILE: windows of decompressed text are cut at their last line break and handed to
-// fwgpu_trainer_digest_text.  Stops at the first line that is not an example, like digest_text.
-int fwgpu_trainer_digest_file(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cache *cache, const char *filename,
-                              uint32_t threads, uint64_t *n_examples) {
-    if (!tr || !parser || !filename) return fail(FWGPU_ERR_INVALID, "NULL argument");
+}  // extern "C"
+
+// main.rs:213-270 over an input FILE: windows of decompressed text are cut at their last line break and handed to `digest`
+// (fwgpu_trainer_digest_text or its device form).  Stops at the first line that is not an example, like digest_text.
+template <class Digest>
+static int digest_file_windows(const char *filename, uint64_t *n_examples, Digest digest) {
     fwgpu_input *in = nullptr;
     int rc = fwgpu_input_open(filename, &in);
     if (rc) return rc;
@@ -187,7 +188,7 @@ int fwgpu_trainer_digest_file(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cac
             }
         }
         uint64_t n = 0, used = 0;
-        rc = fwgpu_trainer_digest_text(tr, parser, cache, buf.get(), cut, threads, &n, &used);
+        rc = digest(buf.get(), cut, &n, &used);
         total += n;
         if (n_examples) *n_examples = total;
         if (rc != FWGPU_OK || used < cut) return rc;
@@ -196,6 +197,23 @@ int fwgpu_trainer_digest_file(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cac
     }
     if (n_examples) *n_examples = total;
     return FWGPU_OK;
+}
+
+extern "C" {
+
+int fwgpu_trainer_digest_file(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cache *cache, const char *filename,
+                              uint32_t threads, uint64_t *n_examples) {
+    if (!tr || !parser || !filename) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    return digest_file_windows(filename, n_examples, [&](const char *text, uint64_t len, uint64_t *n, uint64_t *used) {
+        return fwgpu_trainer_digest_text(tr, parser, cache, text, len, threads, n, used);
+    });
+}
+
+int fwgpu_trainer_digest_file_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, fwgpu_cache *cache, const char *filename, uint64_t *n_examples) {
+    if (!tr || !tp || !filename) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    return digest_file_windows(filename, n_examples, [&](const char *text, uint64_t len, uint64_t *n, uint64_t *used) {
+        return fwgpu_trainer_digest_text_device(tr, tp, cache, text, len, n, used);
+    });
 }
 
 }  // extern "C"

@@ -686,6 +686,7 @@ static bool batch_fits_fused_kernel(fwgpu_batch *b) {
 void keep_host_copy_if_oversize(fwgpu_batch *b, HostBatch &&hb) {
     if (hb.max_ffm > 4096 || hb.max_lr > 4096 || !batch_fits_fused_kernel(b)) b->host_copy.reset(new HostBatch(std::move(hb)));
 }
+bool record_batch_is_oversize(fwgpu_batch *b) { return !batch_fits_fused_kernel(b); }
 // ... a RECORD batch (just uploaded: max_ffm / max_lr are known) with a record that translates to more entries than that: translated on the host
 int record_batch_host_copy_if_oversize(fwgpu_regressor *r, const fwgpu_translator_config *t, fwgpu_batch *b, const uint32_t *records,
                                        const uint64_t *rec_off, uint32_t n) {

@@ -3,6 +3,7 @@
 // stop and message is the host parser's.  Order of a chunk: status kernel -> {status, length} per line to the host -> host parser on
 // the flagged lines, which fixes their lengths and finds the stop -> offsets -> write kernel -> host-parsed records copied in.
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -43,6 +44,12 @@ struct HostRecord {
     uint32_t line;
     uint64_t off;  // where it goes, in words from the call's first record
     std::vector<uint32_t> words;
+};
+
+struct TrainSet {  // what the launches of one piece read and write; reused when they have retired
+    DevBuf records, rec_off, pred, work;
+    std::vector<uint32_t> host_words;  // the host-parsed records of the piece, back to back (source of asynchronous copies: kept until the set's next piece)
+    std::vector<uint4> host_status;    // ... and their status entries
 };
 
 struct LineMode {  // what the kernels get beyond the text: all zero for fwgpu_text_parser_parse_buffer
@@ -86,6 +93,14 @@ struct fwgpu_text_parser {
     std::vector<uint64_t> li_off;
     std::vector<fwgpu_candidate_info> li_info;
     size_t li_chunks = 0;
+    // training from text (text_train_*): two sets of launch buffers that alternate piece by piece, the plan's scratch, what the host reads of a plan
+    TrainSet train[2];
+    DevBuf plan_tmp, plan_out, host_list;
+    uint64_t *plan_host = nullptr;  // pinned: window statistics, then the host lines' offsets
+    size_t plan_host_cap = 0;
+    std::vector<uint32_t> h_host_list;
+    fwgpu_translator_config train_t{};  // borrowed from text_train_begin's caller for the length of its call
+    uint64_t wait_ns = 0;               // host time spent waiting for `stream` since the last call began
 };
 
 namespace fwgpu {
@@ -97,6 +112,15 @@ struct RunResult {
     size_t n_chunks = 0;
     std::vector<uint64_t> rec_off;  // filled when the caller gave none
 };
+
+// the host waits for the parser's stream; the time is kept for fwgpu_text_parser_last_wait_ns
+int wait_stream(fwgpu_text_parser *tp) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipError_t e = hipStreamSynchronize(tp->stream);
+    tp->wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("hipStreamSynchronize(parser stream): ") + hipGetErrorString(e));
+    return FWGPU_OK;
+}
 
 int upload_text(fwgpu_text_parser *tp, TextChunk &ch, const char *text, uint32_t len) {
     int rc = ch.text.ensure((size_t)len + kTextPad + 16);
@@ -114,8 +138,8 @@ int upload_text(fwgpu_text_parser *tp, TextChunk &ch, const char *text, uint32_t
     return FWGPU_OK;
 }
 
-// line index + status pass of a chunk already on the device; leaves h_status
-int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail) {
+// line index + status pass of a chunk already on the device; leaves h_status (fetch == false: the statuses stay on the device, nobody waits for the pass)
+int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail, bool fetch = true) {
     const uint32_t n16 = (ch.len + 15) / 16;
     int rc = ch.cnt.ensure(4 * ((size_t)n16 + 1));
     if (!rc) rc = ch.rank.ensure(4 * ((size_t)n16 + 1));
@@ -125,7 +149,7 @@ int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail) {
     FWGPU_HIP(text_count_lines(ch.text.as<unsigned char>(), ch.len, ch.cnt.as<uint32_t>(), ch.rank.as<uint32_t>(), tp->scan_tmp.p, tmp, tp->stream));
     uint32_t newlines = 0;
     FWGPU_HIP(hipMemcpyAsync(&newlines, ch.rank.as<uint32_t>() + n16, 4, hipMemcpyDeviceToHost, tp->stream));
-    FWGPU_HIP(hipStreamSynchronize(tp->stream));
+    if ((rc = wait_stream(tp))) return rc;
     ch.nlines = newlines + (tail ? 1u : 0u);
     ch.h_lstart.clear();
     ch.host_recs.clear();
@@ -146,6 +170,7 @@ int chunk_status(fwgpu_text_parser *tp, TextChunk &ch, bool tail) {
     a.long_list = ch.long_list.as<uint32_t>();
     a.long_count = tp->long_count;
     FWGPU_HIP(text_parse_launch(a, false, tp->stream));
+    if (!fetch) return FWGPU_OK;
     ch.h_status.resize(ch.nlines);
     if (ch.nlines) FWGPU_HIP(hipMemcpyAsync(ch.h_status.data(), ch.status.p, 16 * (size_t)ch.nlines, hipMemcpyDeviceToHost, tp->stream));
     FWGPU_HIP(hipStreamSynchronize(tp->stream));
@@ -156,8 +181,7 @@ int fetch_line_starts(fwgpu_text_parser *tp, TextChunk &ch) {
     if (!ch.h_lstart.empty()) return FWGPU_OK;
     ch.h_lstart.resize((size_t)ch.nlines + 1);
     FWGPU_HIP(hipMemcpyAsync(ch.h_lstart.data(), ch.lstart.p, 4 * ((size_t)ch.nlines + 1), hipMemcpyDeviceToHost, tp->stream));
-    FWGPU_HIP(hipStreamSynchronize(tp->stream));
-    return FWGPU_OK;
+    return wait_stream(tp);
 }
 
 // the host parser on one line, exactly as fwgpu_parser_parse_buffer meets it; the record is left in tp->line_words
@@ -494,8 +518,148 @@ int text_lines_place(fwgpu_text_parser *tp, uint32_t *d_records) {
     return FWGPU_OK;
 }
 
-namespace {
-}  // namespace
+// ---- training from text (trainer.cpp fwgpu_trainer_digest_text_device): a piece of text -> records, offsets and launch statistics in one of the
+// parser's two sets of device buffers.  Status pass, then the host parses exactly the lines the kernel listed as NEEDS_HOST and writes their
+// {HOST_DONE, length, LR entries, FFM entries} into the status array, then text_batch_plan places every record and sums every launch window, then
+// the write pass and the copies of the host's records.  The host reads a line count, the number of host lines and a few words per window.
+int text_train_begin(fwgpu_text_parser *tp, const fwgpu_translator_config *t, int device) {
+    if (!tp || !t) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (tp->device != device) return fail(FWGPU_ERR_INVALID, "training from text: parser and regressor are on different devices");
+    FWGPU_HIP(hipSetDevice(tp->device));
+    tp->last_lines = tp->last_host_lines = 0;
+    tp->wait_ns = 0;
+    tp->mode = LineMode();
+    tp->train_t = *t;
+    return upload_side(tp, t, nullptr);
+}
+
+hipStream_t text_train_stream(fwgpu_text_parser *tp) { return tp->stream; }
+int text_train_wait(fwgpu_text_parser *tp) { return wait_stream(tp); }
+
+int text_train_piece(fwgpu_text_parser *tp, const char *text, uint64_t len, int set, uint32_t micro_batch, uint32_t learn_before, TextTrainPiece *out) {
+    *out = TextTrainPiece();
+    if (len == 0) return FWGPU_OK;
+    if (tp->chunks.empty()) tp->chunks.emplace_back(new TextChunk());
+    TextChunk &ch = *tp->chunks[0];
+    TrainSet &S = tp->train[set];
+    S.host_words.clear();
+    S.host_status.clear();
+    const bool device_scan = len <= kChunkBytes;  // (the caller cuts at line breaks: anything longer is ONE line, the host's)
+    int rc = FWGPU_OK;
+    uint32_t n_host = 0;
+    uint32_t *d_count = tp->long_count + 4;
+    if (device_scan) {
+        if ((rc = upload_text(tp, ch, text, (uint32_t)len))) return rc;
+        if ((rc = chunk_status(tp, ch, text[len - 1] != '\n', /*fetch=*/false))) return rc;
+        const size_t tmp = text_plan_temp_bytes(ch.nlines);
+        if ((rc = tp->plan_tmp.ensure(tmp))) return rc;
+        if ((rc = tp->host_list.ensure(4 * std::max<size_t>(ch.nlines, 1)))) return rc;
+        FWGPU_HIP(text_host_lines(ch.status.as<uint4>(), ch.nlines, tp->host_list.as<uint32_t>(), d_count, tp->plan_tmp.p, tmp, tp->stream));
+        FWGPU_HIP(hipMemcpyAsync(&n_host, d_count, 4, hipMemcpyDeviceToHost, tp->stream));
+        if ((rc = wait_stream(tp))) return rc;
+        if (n_host > ch.nlines) return fail(FWGPU_ERR_DEVICE, "training from text: more host lines than lines");
+        tp->h_host_list.resize(n_host);
+        if (n_host) {
+            FWGPU_HIP(hipMemcpyAsync(tp->h_host_list.data(), tp->host_list.p, 4 * (size_t)n_host, hipMemcpyDeviceToHost, tp->stream));
+            if ((rc = fetch_line_starts(tp, ch))) return rc;  // (waits for the list too)
+        }
+    } else {
+        ch.len = 0;
+        ch.nlines = n_host = 1;
+        ch.n_used = 0;
+        ch.host_recs.clear();
+        ch.h_lstart.assign({0u, 0u});
+        if ((rc = ch.status.ensure(16))) return rc;
+        if ((rc = tp->host_list.ensure(4))) return rc;
+        if ((rc = tp->plan_tmp.ensure(text_plan_temp_bytes(1)))) return rc;
+        FWGPU_HIP(hipMemsetAsync(tp->host_list.p, 0, 4, tp->stream));
+        tp->h_host_list.assign(1, 0u);
+    }
+    const uint32_t nlines = ch.nlines;
+    uint32_t n_take = nlines;
+    // ---- the host's lines, in order; the first that is no example ends the take
+    struct Placed { uint32_t line; uint64_t at, n; };  // in S.host_words
+    std::vector<Placed> placed;
+    for (uint32_t j = 0; j < n_host; j++) {
+        const uint32_t i = tp->h_host_list[j];
+        const char *line = device_scan ? text + ch.h_lstart[i] : text;
+        const uint64_t size = device_scan ? ch.h_lstart[i + 1] - ch.h_lstart[i] : len;
+        rc = host_line(tp, line, size);
+        if (rc != FWGPU_OK) {
+            out->stop = rc;
+            out->stop_msg = fwgpu_last_error();
+            n_take = i;
+            n_host = j;
+            break;
+        }
+        uint32_t n_lr = 0, n_ffm = 0;
+        if ((rc = count_record(&tp->train_t, tp->line_words.data(), (uint32_t)tp->line_words.size(), &n_lr, &n_ffm))) return rc;
+        placed.push_back({i, S.host_words.size(), tp->line_words.size()});
+        S.host_words.insert(S.host_words.end(), tp->line_words.begin(), tp->line_words.end());
+        S.host_status.push_back(make_uint4(kTextHostDone, (uint32_t)tp->line_words.size(), n_lr, n_ffm));
+    }
+    for (uint32_t j = 0; j < n_host; j++)
+        FWGPU_HIP(hipMemcpyAsync(ch.status.as<uint4>() + placed[j].line, &S.host_status[j], 16, hipMemcpyHostToDevice, tp->stream));
+    tp->last_lines += n_take + (out->stop != FWGPU_OK ? 1 : 0);
+    out->n_lines = nlines;
+    out->n_take = n_take;
+    out->consumed = n_take < nlines ? ch.h_lstart[n_take] : len;
+    if (n_take == 0) return FWGPU_OK;
+    // ---- the plan
+    const TextPlanShape shape = text_plan_shape(n_take, micro_batch, learn_before);
+    const size_t n_out = (size_t)kTextPlanStats * shape.n_windows + n_host;
+    if ((rc = S.rec_off.ensure(8 * ((size_t)n_take + 1)))) return rc;
+    if ((rc = tp->plan_out.ensure(8 * n_out))) return rc;
+    if (tp->plan_host_cap < n_out) {
+        if (tp->plan_host) (void)hipHostFree(tp->plan_host);
+        tp->plan_host = nullptr;
+        tp->plan_host_cap = 0;
+        FWGPU_HIP(hipHostMalloc((void **)&tp->plan_host, 8 * (n_out * 2 + 64), hipHostMallocDefault));
+        tp->plan_host_cap = n_out * 2 + 64;
+    }
+    uint64_t *d_stats = tp->plan_out.as<uint64_t>(), *d_host_off = d_stats + (size_t)kTextPlanStats * shape.n_windows;
+    FWGPU_HIP(text_batch_plan(ch.status.as<uint4>(), n_take, micro_batch, learn_before, S.rec_off.as<uint64_t>(), d_stats, tp->host_list.as<uint32_t>(), n_host,
+                              d_host_off, tp->plan_tmp.p, tp->plan_tmp.cap, tp->stream));
+    FWGPU_HIP(hipMemcpyAsync(tp->plan_host, d_stats, 8 * n_out, hipMemcpyDeviceToHost, tp->stream));
+    if ((rc = wait_stream(tp))) return rc;
+    uint64_t n_words = 0;
+    for (uint32_t w = 0; w < shape.n_windows; w++) n_words += tp->plan_host[(size_t)kTextPlanStats * w + 1];
+    // ---- placement
+    if ((rc = S.records.ensure(4 * std::max<uint64_t>(n_words, 1)))) return rc;
+    if ((rc = S.pred.ensure(4 * (size_t)n_take))) return rc;
+    if ((rc = S.work.ensure(4 * (size_t)kTextTrainWorkStride * shape.n_windows))) return rc;
+    if (device_scan) {
+        TextParseArgs a{};
+        a.text = ch.text.as<unsigned char>();
+        a.lstart = ch.lstart.as<uint32_t>();
+        a.nlines = nlines;
+        a.ns = tp->ns;
+        a.tr = tp->mode.tr;
+        a.status = ch.status.as<uint4>();
+        a.n_used = n_take;
+        a.dst_off = S.rec_off.as<uint64_t>();
+        a.dst = S.records.as<uint32_t>();
+        a.long_list = ch.long_list.as<uint32_t>();
+        a.long_count = tp->long_count;
+        FWGPU_HIP(text_parse_launch(a, true, tp->stream));
+    }
+    const uint64_t *host_off = tp->plan_host + (size_t)kTextPlanStats * shape.n_windows;
+    for (uint32_t j = 0; j < n_host; j++) {
+        if (host_off[j] + placed[j].n > n_words) return fail(FWGPU_ERR_DEVICE, "training from text: a host line's record lies outside the piece's records");
+        FWGPU_HIP(hipMemcpyAsync(S.records.as<uint32_t>() + host_off[j], S.host_words.data() + placed[j].at, 4 * (size_t)placed[j].n, hipMemcpyHostToDevice, tp->stream));
+    }
+    out->n_learn = shape.n_learn;
+    out->n_windows_learn = shape.n_windows_learn;
+    out->n_windows = shape.n_windows;
+    out->n_words = n_words;
+    out->win_stats = tp->plan_host;
+    out->d_records = S.records.as<uint32_t>();
+    out->d_rec_off = S.rec_off.as<uint64_t>();
+    out->d_pred = S.pred.as<float>();
+    out->d_work = S.work.as<uint32_t>();
+    return FWGPU_OK;
+}
+
 }  // namespace fwgpu
 
 extern "C" {
@@ -574,6 +738,7 @@ void fwgpu_text_parser_free(fwgpu_text_parser *tp) {
         if (tp->pinned_free[k]) (void)hipEventDestroy(tp->pinned_free[k]);
     }
     if (tp->long_count) (void)hipFree(tp->long_count);
+    if (tp->plan_host) (void)hipHostFree(tp->plan_host);
     if (tp->ns_blob) (void)hipFree(tp->ns_blob);
     if (tp->stream) (void)hipStreamDestroy(tp->stream);
     if (tp->host) fwgpu_parser_free(tp->host);
@@ -623,6 +788,48 @@ int fwgpu_text_parser_last_lines(const fwgpu_text_parser *tp, uint64_t *lines, u
     if (!tp) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (lines) *lines = tp->last_lines;
     if (host_lines) *host_lines = tp->last_host_lines;
+    return FWGPU_OK;
+}
+
+int fwgpu_text_parser_last_wait_ns(const fwgpu_text_parser *tp, uint64_t *ns) {
+    if (!tp || !ns) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *ns = tp->wait_ns;
+    return FWGPU_OK;
+}
+
+// text_batch_plan (textparse.hip) on host arrays, for tests against a plain restatement
+int fwgpu_debug_text_plan(const uint32_t *status4, uint32_t nlines, uint32_t n_take, uint32_t micro_batch, uint32_t learn_before_holdout, uint64_t *dst_off,
+                          uint64_t *rec_off, uint32_t *n_windows, uint64_t *window_stats, uint32_t *host_lines, uint32_t *n_host_lines, void *stream_) {
+    if ((nlines && !status4) || !rec_off || !n_windows || !n_host_lines || (nlines && !host_lines) || (n_take && !dst_off))
+        return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (n_take > nlines || micro_batch == 0) return fail(FWGPU_ERR_INVALID, "text_plan: n_take > nlines or micro_batch == 0");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const TextPlanShape shape = text_plan_shape(n_take, micro_batch, learn_before_holdout);
+    if (shape.n_windows && !window_stats) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    DevBuf d_status, d_off, d_stats, d_list, d_count, d_host_off, tmp;
+    int rc = d_status.ensure(16 * std::max<size_t>(nlines, 1));
+    if (!rc) rc = d_off.ensure(8 * ((size_t)n_take + 1));
+    if (!rc) rc = d_stats.ensure(8 * kTextPlanStats * std::max<size_t>(shape.n_windows, 1));
+    if (!rc) rc = d_list.ensure(4 * std::max<size_t>(nlines, 1));
+    if (!rc) rc = d_host_off.ensure(8 * std::max<size_t>(nlines, 1));
+    if (!rc) rc = d_count.ensure(4);
+    if (!rc) rc = tmp.ensure(text_plan_temp_bytes(nlines));
+    if (rc) return rc;
+    if (nlines) FWGPU_HIP(hipMemcpyAsync(d_status.p, status4, 16 * (size_t)nlines, hipMemcpyHostToDevice, stream));
+    FWGPU_HIP(text_host_lines(d_status.as<uint4>(), nlines, d_list.as<uint32_t>(), d_count.as<uint32_t>(), tmp.p, tmp.cap, stream));
+    uint32_t n_host = 0;
+    FWGPU_HIP(hipMemcpyAsync(&n_host, d_count.p, 4, hipMemcpyDeviceToHost, stream));
+    FWGPU_HIP(hipStreamSynchronize(stream));
+    if (n_host > nlines) return fail(FWGPU_ERR_DEVICE, "text_plan: more host lines than lines");
+    FWGPU_HIP(text_batch_plan(d_status.as<uint4>(), n_take, micro_batch, learn_before_holdout, d_off.as<uint64_t>(), d_stats.as<uint64_t>(), d_list.as<uint32_t>(), n_host,
+                              d_host_off.as<uint64_t>(), tmp.p, tmp.cap, stream));
+    FWGPU_HIP(hipMemcpyAsync(rec_off, d_off.p, 8 * ((size_t)n_take + 1), hipMemcpyDeviceToHost, stream));
+    if (shape.n_windows) FWGPU_HIP(hipMemcpyAsync(window_stats, d_stats.p, 8 * (size_t)kTextPlanStats * shape.n_windows, hipMemcpyDeviceToHost, stream));
+    if (n_host) FWGPU_HIP(hipMemcpyAsync(host_lines, d_list.p, 4 * (size_t)n_host, hipMemcpyDeviceToHost, stream));
+    FWGPU_HIP(hipStreamSynchronize(stream));
+    if (n_take) std::memcpy(dst_off, rec_off, 8 * (size_t)n_take);
+    *n_windows = shape.n_windows;
+    *n_host_lines = n_host;
     return FWGPU_OK;
 }
 

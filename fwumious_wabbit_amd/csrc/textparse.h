@@ -8,6 +8,8 @@
 namespace fwgpu {
 
 constexpr uint32_t kTextDeviceOk = 1, kTextNeedsHost = 2;  // per-line status
+constexpr uint32_t kTextHostDone = 3;  // training from text: the host parsed the line and wrote its record length and entry counts into the status entry
+constexpr uint32_t kTextNoHoldout = 0xffffffffu;  // text_batch_plan's learn_before: every taken line may be learned
 constexpr uint32_t kTextMaxNamespaces = 256;               // slot words a wave keeps in LDS; a larger map goes to the host whole
 constexpr uint32_t kTextPad = 64;                          // readable bytes the text allocation has after its last byte
 
@@ -66,5 +68,35 @@ size_t text_scan_temp_bytes(uint32_t n16_max);
 hipError_t text_count_lines(const unsigned char *text, uint32_t len, uint32_t *cnt, uint32_t *rank, void *tmp, size_t tmp_bytes, hipStream_t stream);
 hipError_t text_line_index(const unsigned char *text, uint32_t len, const uint32_t *rank, int tail, uint32_t *lstart, hipStream_t stream);
 hipError_t text_parse_launch(const TextParseArgs &a, bool write, hipStream_t stream);
+
+// ---- micro-batch plan of a piece (training from text): placement, per-launch statistics and the host's lines, all from the status array.
+// The first n_take lines are taken.  They are cut into launch windows of at most micro_batch lines, and no window straddles line learn_before
+// (the first line that is predicted instead of learned; kTextNoHoldout: none): windows [0, n_windows_learn) cover lines [0, n_learn), the others
+// the rest.  A line counts with its status entry's {length, LR entries, FFM entries} when its status is DEVICE_OK or HOST_DONE, with zeros otherwise.
+struct TextPlanShape {
+    uint32_t n_learn, n_windows_learn, n_windows;
+    __host__ __device__ void window(uint32_t w, uint32_t micro_batch, uint32_t n_take, uint32_t *first, uint32_t *end) const {
+        const bool learn = w < n_windows_learn;
+        const uint64_t f = learn ? (uint64_t)w * micro_batch : n_learn + (uint64_t)(w - n_windows_learn) * micro_batch;
+        const uint64_t lim = learn ? n_learn : n_take, e = f + micro_batch < lim ? f + micro_batch : lim;
+        *first = (uint32_t)f;
+        *end = (uint32_t)e;
+    }
+};
+inline TextPlanShape text_plan_shape(uint32_t n_take, uint32_t micro_batch, uint32_t learn_before) {
+    TextPlanShape s;
+    s.n_learn = learn_before < n_take ? learn_before : n_take;
+    s.n_windows_learn = (uint32_t)(((uint64_t)s.n_learn + micro_batch - 1) / micro_batch);
+    s.n_windows = s.n_windows_learn + (uint32_t)(((uint64_t)(n_take - s.n_learn) + micro_batch - 1) / micro_batch);
+    return s;
+}
+constexpr uint32_t kTextPlanStats = 7;  // per window: examples, words, max_lr, max_ffm, max_rec, tot_lr, tot_ffm (RecordStats of the window's records)
+size_t text_plan_temp_bytes(uint32_t nlines_max);
+// the NEEDS_HOST lines of [0, nlines), in order, and their number (device memory)
+hipError_t text_host_lines(const uint4 *status, uint32_t nlines, uint32_t *host_lines, uint32_t *count, void *tmp, size_t tmp_bytes, hipStream_t stream);
+// rec_off[0 .. n_take]: word offset of every taken line's record (the write pass's dst_off, the launches' rec_off) and their total;
+// win_stats[kTextPlanStats * n_windows]; host_off[j] = rec_off[host_lines[j]] for the first n_host listed lines (0 for a line beyond n_take)
+hipError_t text_batch_plan(const uint4 *status, uint32_t n_take, uint32_t micro_batch, uint32_t learn_before, uint64_t *rec_off, uint64_t *win_stats,
+                           const uint32_t *host_lines, uint32_t n_host, uint64_t *host_off, void *tmp, size_t tmp_bytes, hipStream_t stream);
 
 }  // namespace fwgpu

@@ -18,7 +18,11 @@
 // words 1 and 2 and NO_FEATURES in every slot whose merged form equals the context's slot word -- fwgpu_parser_parse_candidate's
 // candidate-only record (parser.cpp).  With a translator (TextParseArgs::tr) the status pass also counts the line's LR and FFM entries
 // (translate.cpp count_record) and, in candidate mode, decides the cache's record rule (regressor.cpp block_cache_record_ok) exactly.
+//
+// Micro-batch plan (training from text, textparse.h): from a piece's status array alone, a rocPRIM select lists the NEEDS_HOST lines, a rocPRIM scan
+// places every taken line's record, and one workgroup per launch window sums what the host would otherwise count from the records.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -447,7 +451,104 @@ __global__ void text_line_starts(const uint4 *text, uint32_t n16, uint32_t len, 
     }
 }
 
+// ---- micro-batch plan (textparse.h): one scan for the placement, one workgroup per launch window for its statistics
+__host__ __device__ inline bool line_counts(uint32_t status_x) {
+    const uint32_t s = status_x & 0xffu;
+    return s == kTextDeviceOk || s == kTextHostDone;
+}
+
+struct PlanLineLen {  // record length of line i as the placement counts it; line n_take (one past) closes the scan
+    const uint4 *status;
+    uint32_t n_take;
+    __host__ __device__ uint64_t operator()(uint32_t i) const {
+        if (i >= n_take) return 0;
+        const uint4 s = status[i];
+        return line_counts(s.x) ? (uint64_t)s.y : 0ull;
+    }
+};
+
+struct PlanNeedsHost {
+    const uint4 *status;
+    __host__ __device__ bool operator()(uint32_t i) const { return (status[i].x & 0xffu) == kTextNeedsHost; }
+};
+
+__global__ void text_plan_windows(const uint4 *status, uint32_t n_take, uint32_t micro_batch, TextPlanShape shape, const uint64_t *rec_off, uint64_t *win_stats) {
+    __shared__ uint32_t s_max[3][4];
+    __shared__ unsigned long long s_tot[2][4];
+    const uint32_t w = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    uint32_t first, end;
+    shape.window(w, micro_batch, n_take, &first, &end);
+    uint32_t mx[3] = {0, 0, 0};
+    unsigned long long tot[2] = {0, 0};
+    for (uint32_t i = first + threadIdx.x; i < end; i += blockDim.x) {
+        const uint4 s = status[i];
+        if (!line_counts(s.x)) continue;
+        mx[0] = max(mx[0], s.z);
+        mx[1] = max(mx[1], s.w);
+        mx[2] = max(mx[2], s.y);
+        tot[0] += s.z;
+        tot[1] += s.w;
+    }
+    for (int o = 32; o; o >>= 1) {
+        for (int q = 0; q < 3; q++) mx[q] = max(mx[q], (uint32_t)__shfl_xor((int)mx[q], o, 64));
+        for (int q = 0; q < 2; q++) tot[q] += __shfl_xor(tot[q], o, 64);
+    }
+    if (lane == 0) {
+        for (int q = 0; q < 3; q++) s_max[q][wave] = mx[q];
+        for (int q = 0; q < 2; q++) s_tot[q][wave] = tot[q];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (uint32_t v = 1; v < nwaves; v++) {
+        for (int q = 0; q < 3; q++) mx[q] = max(mx[q], s_max[q][v]);
+        for (int q = 0; q < 2; q++) tot[q] += s_tot[q][v];
+    }
+    uint64_t *o = win_stats + (size_t)kTextPlanStats * w;
+    o[0] = end - first;
+    o[1] = rec_off[end] - rec_off[first];
+    o[2] = mx[0];
+    o[3] = mx[1];
+    o[4] = mx[2];
+    o[5] = tot[0];
+    o[6] = tot[1];
+}
+
+__global__ void text_plan_host_off(const uint64_t *rec_off, uint32_t n_take, const uint32_t *host_lines, uint32_t n_host, uint64_t *host_off) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_host) return;
+    const uint32_t line = host_lines[j];
+    host_off[j] = line < n_take ? rec_off[line] : 0ull;
+}
+
 }  // namespace
+
+size_t text_plan_temp_bytes(uint32_t nlines_max) {
+    size_t a = 0, b = 0;
+    (void)rocprim::exclusive_scan(nullptr, a, rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), PlanLineLen{nullptr, 0}), (uint64_t *)nullptr,
+                                  (uint64_t)0, (size_t)nlines_max + 1, rocprim::plus<uint64_t>(), (hipStream_t)0);
+    (void)rocprim::select(nullptr, b, rocprim::counting_iterator<uint32_t>(0), rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), PlanNeedsHost{nullptr}),
+                          (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)nlines_max, (hipStream_t)0);
+    return std::max<size_t>(std::max(a, b), 256);
+}
+
+hipError_t text_host_lines(const uint4 *status, uint32_t nlines, uint32_t *host_lines, uint32_t *count, void *tmp, size_t tmp_bytes, hipStream_t stream) {
+    if (nlines == 0) return hipMemsetAsync(count, 0, 4, stream);
+    hipError_t e = rocprim::select(tmp, tmp_bytes, rocprim::counting_iterator<uint32_t>(0),
+                                   rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), PlanNeedsHost{status}), host_lines, count, (size_t)nlines, stream);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t text_batch_plan(const uint4 *status, uint32_t n_take, uint32_t micro_batch, uint32_t learn_before, uint64_t *rec_off, uint64_t *win_stats,
+                           const uint32_t *host_lines, uint32_t n_host, uint64_t *host_off, void *tmp, size_t tmp_bytes, hipStream_t stream) {
+    if (micro_batch == 0) return hipErrorInvalidValue;
+    hipError_t e = rocprim::exclusive_scan(tmp, tmp_bytes, rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), PlanLineLen{status, n_take}), rec_off,
+                                           (uint64_t)0, (size_t)n_take + 1, rocprim::plus<uint64_t>(), stream);
+    if (e != hipSuccess) return e;
+    const TextPlanShape shape = text_plan_shape(n_take, micro_batch, learn_before);
+    if (shape.n_windows) text_plan_windows<<<shape.n_windows, micro_batch <= 64 ? 64 : 256, 0, stream>>>(status, n_take, micro_batch, shape, rec_off, win_stats);
+    if (n_host) text_plan_host_off<<<(n_host + 255) / 256, 256, 0, stream>>>(rec_off, n_take, host_lines, n_host, host_off);
+    return hipGetLastError();
+}
 
 size_t text_scan_temp_bytes(uint32_t n16_max) {
     size_t b = 0;

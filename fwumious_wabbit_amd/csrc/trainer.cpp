@@ -2,6 +2,7 @@
 // shipped to HBM in micro-batches and translated + learned on the device (the stage phase of the example kernel is
 // FeatureBufferTranslator::translate).  Two staging/device buffers alternate so that filling and uploading
 // micro-batch i+1 overlaps the kernel of micro-batch i.  The host only validates slot words (count_record).
+// fwgpu_trainer_digest_text_device feeds the same two slots from the device parser's buffers instead (launch_text_piece).
 #include <string.h>
 
 #include <string>
@@ -12,6 +13,7 @@
 #include <thread>
 
 #include "fwgpu_internal.h"
+#include "textparse.h"
 
 using namespace fwgpu;
 
@@ -53,6 +55,9 @@ struct fwgpu_trainer {
     // host threads kept between calls: staging copies of fwgpu_digest_records, parser threads of
     // fwgpu_trainer_digest_text.  Two pools: a chunk of text is parsed while the previous chunk's records are digested.
     Workers copy_pool, parse_pool;
+    // device text route: the launch windows of the piece in slot c (views of the parser's buffers), and the batch that owns the translator's device arrays
+    std::vector<std::unique_ptr<fwgpu_batch>> views[2];
+    fwgpu_batch *text_tr = nullptr;
 };
 
 static bool predict_mode(const fwgpu_trainer *tr) {  // for the NEXT example (number seen + 1)
@@ -69,12 +74,9 @@ static int retire(fwgpu_trainer *tr, int c) {
     return FWGPU_OK;
 }
 
-static int flush(fwgpu_trainer *tr, bool predict = false) {
-    const int c = tr->cur;
-    const uint32_t n = (uint32_t)(tr->off[c].size() - 1);
-    if (n == 0) return FWGPU_OK;
+// first half of a host-fed launch: the records staged for slot c go into its device buffer (copy stream -> compute stream)
+static int stage_slot(fwgpu_trainer *tr, int c, uint32_t n) {
     fwgpu_regressor *r = tr->r;
-    FWGPU_HIP(hipSetDevice(r->device));
     // device buffer c may still be read by its previous kernel
     int rrc = retire(tr, c);
     if (rrc) return rrc;
@@ -95,31 +97,112 @@ static int flush(fwgpu_trainer *tr, bool predict = false) {
     if ((rc = record_batch_host_copy_if_oversize(r, &tr->t, b, tr->rec[c], tr->off[c].data(), n))) return rc;
     FWGPU_HIP(hipEventRecord(tr->uploaded[c], tr->copy_stream));
     FWGPU_HIP(hipStreamWaitEvent(tr->stream, tr->uploaded[c], 0));
-    rc = fwgpu_learn_batch(r, b, FWGPU_MODE_HOGWILD, predict ? 0 : 1, tr->stream);
-    if (rc) return rc;
-    if (predict) {
-        if (tr->pred_cap[c] < n) {
+    return FWGPU_OK;
+}
+
+// second half, shared by the host-fed and the device text route: slot c's launches are on the compute stream; the predictions of its n_pred
+// examples that were not learned (d_pred, NULL: none) come back with them, the slot's event closes it and the other slot is the current one
+static int close_slot(fwgpu_trainer *tr, int c, const float *d_pred, uint32_t n_pred) {
+    if (d_pred && n_pred) {
+        if (tr->pred_cap[c] < n_pred) {
             if (tr->pred_host[c]) (void)hipHostFree(tr->pred_host[c]);
             tr->pred_host[c] = nullptr;
-            FWGPU_HIP(hipHostMalloc((void **)&tr->pred_host[c], (size_t)std::max(n, tr->micro_batch) * 4, hipHostMallocDefault));
-            tr->pred_cap[c] = std::max(n, tr->micro_batch);
+            tr->pred_cap[c] = 0;
+            FWGPU_HIP(hipHostMalloc((void **)&tr->pred_host[c], (size_t)std::max(n_pred, tr->micro_batch) * 4, hipHostMallocDefault));
+            tr->pred_cap[c] = std::max(n_pred, tr->micro_batch);
         }
-        FWGPU_HIP(hipMemcpyAsync(tr->pred_host[c], b->pred, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream));
+        FWGPU_HIP(hipMemcpyAsync(tr->pred_host[c], d_pred, (size_t)n_pred * 4, hipMemcpyDeviceToHost, tr->stream));
     }
-    tr->slot_predict[c] = predict;
-    tr->slot_n[c] = n;
+    tr->slot_predict[c] = d_pred && n_pred;
+    tr->slot_n[c] = n_pred;
     FWGPU_HIP(hipEventRecord(tr->done[c], tr->stream));
     tr->in_flight[c] = true;
-    // Staging buffer c stays untouched until its copies and kernel are done; switch to the other buffer, which may be
-    // refilled once ITS previous micro-batch has completed.
-    tr->cur ^= 1;
+    tr->cur = c ^ 1;
+    return FWGPU_OK;
+}
+
+// Staging buffer c stays untouched until its copies and kernel are done; the other buffer, now the current one, may be
+// refilled once ITS previous micro-batch has completed.
+static int open_slot(fwgpu_trainer *tr) {
     const int c2 = tr->cur;
-    rrc = retire(tr, c2);
+    int rrc = retire(tr, c2);
     if (rrc) return rrc;
     tr->rec_used[c2] = 0;
     tr->off[c2].assign(1, 0);
     tr->stats[c2] = RecordStats();
     return FWGPU_OK;
+}
+
+static int flush(fwgpu_trainer *tr, bool predict = false) {
+    const int c = tr->cur;
+    const uint32_t n = (uint32_t)(tr->off[c].size() - 1);
+    if (n == 0) return FWGPU_OK;
+    fwgpu_regressor *r = tr->r;
+    FWGPU_HIP(hipSetDevice(r->device));
+    int rc = stage_slot(tr, c, n);
+    if (rc) return rc;
+    fwgpu_batch *b = tr->dev[c];
+    rc = fwgpu_learn_batch(r, b, FWGPU_MODE_HOGWILD, predict ? 0 : 1, tr->stream);
+    if (rc) return rc;
+    if ((rc = close_slot(tr, c, predict ? b->pred : nullptr, n))) return rc;
+    return open_slot(tr);
+}
+
+// ---- device text route: a piece the parser has planned and placed (text_parser.cpp text_train_piece) is launched window by window from the
+// parser's buffers.  A window is a non-owning record batch: rec_off + first into the piece's offsets, its own predictions and work counter.
+static int launch_text_piece(fwgpu_trainer *tr, fwgpu_text_parser *tp, int c, const TextTrainPiece &P) {
+    fwgpu_regressor *r = tr->r;
+    if (!tr->text_tr) {  // (owns the translator's device arrays every window points at)
+        int rc = record_batch_alloc(r, &tr->t, 1, 1, &tr->text_tr);
+        if (rc) return rc;
+    }
+    // the launches wait for the parser's stream, not the host
+    FWGPU_HIP(hipEventRecord(tr->uploaded[c], text_train_stream(tp)));
+    FWGPU_HIP(hipStreamWaitEvent(tr->stream, tr->uploaded[c], 0));
+    std::vector<std::unique_ptr<fwgpu_batch>> &views = tr->views[c];
+    while (views.size() < P.n_windows) views.emplace_back(new fwgpu_batch());
+    TextPlanShape shape;
+    shape.n_learn = P.n_learn;
+    shape.n_windows_learn = P.n_windows_learn;
+    shape.n_windows = P.n_windows;
+    for (uint32_t w = 0; w < P.n_windows; w++) {
+        const uint64_t *st = P.win_stats + (size_t)kTextPlanStats * w;
+        uint32_t first, end;
+        shape.window(w, tr->micro_batch, P.n_take, &first, &end);
+        if (st[0] != end - first) return fail(FWGPU_ERR_DEVICE, "training from text: the plan's windows are not the host's");
+        fwgpu_batch *b = views[w].get();
+        b->owner = r;
+        b->n = b->n_cap = end - first;
+        b->n_lr = st[5];
+        b->n_ffm = st[6];
+        b->n_words = b->words_cap = st[1];
+        b->max_lr = r->cfg.wiring == FWGPU_WIRING_FFM_ONLY ? 0 : (uint32_t)st[2];  // as record_batch_upload leaves a batch
+        b->max_ffm = (uint32_t)st[3];
+        b->max_rec = (uint32_t)st[4];
+        b->aligned4 = true;
+        b->records = P.d_records;
+        b->rec_off = P.d_rec_off + first;
+        b->pred = P.d_pred + first;
+        b->work = P.d_work + (size_t)kTextTrainWorkStride * w;
+        b->tr = tr->text_tr->tr;
+        b->host_copy.reset();
+        if (record_batch_is_oversize(b)) {  // the walk of fwgpu_digest_records, from this launch's records alone
+            std::vector<uint64_t> off((size_t)b->n + 1);
+            std::vector<uint32_t> words((size_t)st[1]);
+            int rc = text_train_wait(tp);
+            if (rc) return rc;
+            FWGPU_HIP(hipMemcpy(off.data(), b->rec_off, 8 * off.size(), hipMemcpyDeviceToHost));
+            const uint64_t w0 = off[0];
+            if (off.back() - w0 != st[1]) return fail(FWGPU_ERR_DEVICE, "training from text: a window's offsets and its word count differ");
+            if (!words.empty()) FWGPU_HIP(hipMemcpy(words.data(), b->records + w0, 4 * words.size(), hipMemcpyDeviceToHost));
+            for (uint64_t &o : off) o -= w0;
+            if ((rc = record_batch_host_copy_if_oversize(r, &tr->t, b, words.data(), off.data(), b->n))) return rc;
+        }
+        int rc = fwgpu_learn_batch(r, b, FWGPU_MODE_HOGWILD, w < P.n_windows_learn ? 1 : 0, tr->stream);
+        if (rc) return rc;
+    }
+    const uint32_t n_pred = P.n_take - P.n_learn;
+    return close_slot(tr, c, n_pred ? P.d_pred + P.n_learn : nullptr, n_pred);
 }
 
 extern "C" {
@@ -451,6 +534,68 @@ int fwgpu_trainer_digest_text(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cac
     return rc;
 }
 
+// fwgpu_trainer_digest_text with the parser on the device (textparse.hip): the text goes up in pieces cut at line breaks, every piece is parsed,
+// cut into micro-batches and placed by kernels on the parser's stream, and launched from there -- piece i + 1 is parsed while piece i is learned.
+// The host parses only the lines the kernel leaves to it and reads a few words per launch; records come back only for a cache that is written
+// and for a launch with an oversize example.
+int fwgpu_trainer_digest_text_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, fwgpu_cache *cache, const char *text, uint64_t len, uint64_t *n_examples,
+                                     uint64_t *consumed) {
+    if (n_examples) *n_examples = 0;
+    if (consumed) *consumed = 0;
+    if (!tr || !tp || (!text && len)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (cache && !fwgpu_cache_is_writing(cache)) return fail(FWGPU_ERR_INVALID, "digest_text_device: the cache is not open for writing");
+    fwgpu_regressor *r = tr->r;
+    FWGPU_HIP(hipSetDevice(r->device));
+    int rc = text_train_begin(tp, &tr->t, r->device);
+    if (rc) return rc;
+    // a micro-batch an earlier fwgpu_digest_records left open goes first (its examples are of one kind, as in fwgpu_finish)
+    if ((rc = flush(tr, tr->testonly || (tr->holdout_after && tr->seen >= tr->holdout_after)))) return rc;
+    uint64_t piece = 8u << 20;
+    if (const char *env = getenv("FWGPU_TRAINER_TEXT_PIECE"))
+        if (atoll(env) > 0) piece = (uint64_t)atoll(env);
+    piece = std::min<uint64_t>(piece, 16u << 20);
+    uint64_t pos = 0, done = 0, used = 0;
+    std::vector<uint32_t> back;
+    std::string msg;
+    while (pos < len && rc == FWGPU_OK) {
+        uint64_t cut = std::min<uint64_t>(len - pos, piece);
+        if (pos + cut < len) {  // cut at the last line break of the window; a line longer than a piece is a piece
+            const void *nl = memrchr(text + pos, '\n', cut);
+            if (!nl) nl = memchr(text + pos + cut, '\n', len - pos - cut);
+            cut = nl ? (uint64_t)(static_cast<const char *>(nl) - (text + pos)) + 1 : len - pos;
+        }
+        const int c = tr->cur;
+        if ((rc = retire(tr, c))) return rc;  // the parser's set c was read by the piece before the last (retired when that slot was opened)
+        uint32_t learn_before = kTextNoHoldout;  // lines of this piece that may still be learned: no launch straddles the hold-out boundary
+        if (tr->testonly) learn_before = 0;
+        else if (tr->holdout_after) learn_before = (uint32_t)std::min<uint64_t>(tr->seen + 1 >= tr->holdout_after ? 0 : tr->holdout_after - 1 - tr->seen, 0xfffffffeu);
+        TextTrainPiece P;
+        if ((rc = text_train_piece(tp, text + pos, cut, c, tr->micro_batch, learn_before, &P))) return rc;
+        if (P.n_take) {
+            if (cache) {  // the one read-back of this route: the piece's records, word for word what the host route appends
+                back.resize((size_t)P.n_words);
+                if ((rc = text_train_wait(tp))) return rc;
+                FWGPU_HIP(hipMemcpy(back.data(), P.d_records, 4 * back.size(), hipMemcpyDeviceToHost));
+                if ((rc = fwgpu_cache_push_records(cache, back.data(), P.n_words))) return rc;
+            }
+            if ((rc = launch_text_piece(tr, tp, c, P))) return rc;
+            if ((rc = open_slot(tr))) return rc;  // (waits for the piece BEFORE this one, whose buffers the next piece takes)
+            tr->seen += P.n_take;
+            done += P.n_take;
+        }
+        used = pos + P.consumed;
+        if (n_examples) *n_examples = done;
+        if (consumed) *consumed = used;
+        if (P.stop != FWGPU_OK) {
+            rc = P.stop;
+            msg = P.stop_msg;
+        }
+        pos += cut;
+    }
+    if (rc != FWGPU_OK && rc != FWGPU_PARSE_FLUSH && rc != FWGPU_PARSE_HOGWILD_LOAD) rc = fail(rc, msg);
+    return rc;
+}
+
 int fwgpu_trainer_set_holdout(fwgpu_trainer *tr, uint64_t holdout_after, int testonly) {
     if (!tr) return fail(FWGPU_ERR_INVALID, "NULL trainer");
     if (tr->off[tr->cur].size() > 1) return fail(FWGPU_ERR_INVALID, "set the hold-out before digesting (or right after fwgpu_finish)");
@@ -488,6 +633,7 @@ int fwgpu_trainer_free(fwgpu_trainer *tr) {
     if (!tr) return FWGPU_OK;
     (void)hipSetDevice(tr->r->device);
     if (tr->stream) (void)hipStreamSynchronize(tr->stream);
+    if (tr->text_tr) fwgpu_batch_free(tr->text_tr);
     for (int i = 0; i < 2; i++) {
         if (tr->dev[i]) fwgpu_batch_free(tr->dev[i]);
         if (tr->rec[i]) (void)hipHostFree(tr->rec[i]);

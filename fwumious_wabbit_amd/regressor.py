@@ -646,6 +646,24 @@ class HogwildTrainer:
             check(rc)
         return n.value, rc
 
+    def digest_text_device(self, dparser, text: bytes, cache=None):
+        """digest_text with the text parsed and cut into micro-batches on the device (dparser: DeviceVowpalParser); same result tuple"""
+        n, used = C.c_uint64(), C.c_uint64()
+        rc = capi.lib().fwgpu_trainer_digest_text_device(self.h, dparser.h, cache.h if cache is not None else None, text, len(text),
+                                                         C.byref(n), C.byref(used))
+        if rc not in (capi.OK, capi.PARSE_FLUSH, capi.PARSE_HOGWILD_LOAD):
+            check(rc)
+        return n.value, used.value, rc
+
+    def digest_file_device(self, dparser, filename: str, cache=None):
+        """digest_file through digest_text_device -> (examples learned, status)"""
+        n = C.c_uint64()
+        rc = capi.lib().fwgpu_trainer_digest_file_device(self.h, dparser.h, cache.h if cache is not None else None, filename.encode(),
+                                                         C.byref(n))
+        if rc not in (capi.OK, capi.PARSE_FLUSH, capi.PARSE_HOGWILD_LOAD):
+            check(rc)
+        return n.value, rc
+
     def block_until_workers_finished(self):
         """hogwild.rs:55-60"""
         check(capi.lib().fwgpu_finish(self.h))

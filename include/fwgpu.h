@@ -659,6 +659,29 @@ int fwgpu_trainer_digest_file(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cac
                               uint32_t threads, uint64_t *n_examples);
 int fwgpu_trainer_digest_text(fwgpu_trainer *tr, fwgpu_parser *parser, fwgpu_cache *cache, const char *text, uint64_t len,
                               uint32_t threads, uint64_t *n_examples, uint64_t *consumed);
+/* fwgpu_trainer_digest_text / _digest_file with the parser on the DEVICE (csrc/textparse.hip): same order, stops, return codes, messages,
+ * *consumed, *n_examples, hold-out protocol and cache contents as the host forms; the command argument comes through
+ * fwgpu_text_parser_command_argument.  The text goes up in pieces cut at line breaks (FWGPU_TRAINER_TEXT_PIECE=<bytes>, default 8 MiB); a piece
+ * is parsed, cut into launches of at most micro_batch examples and placed by kernels on the parser's stream while the piece before it is learned,
+ * and the host parses only the lines the kernel leaves to it (fwgpu_text_parser_last_lines).  micro_batch is a cap here: a piece's last launch,
+ * and the launch before the hold-out boundary, may be shorter.  Everything parsed is launched before the call returns; fwgpu_finish waits.  A
+ * micro-batch left open by fwgpu_digest_records is launched first.  Records are read back only for a cache open for writing (once per piece) and
+ * for a launch that holds an oversize example.  A cache open for reading, or a parser on another device than the regressor's, is
+ * FWGPU_ERR_INVALID.  The parser's buffers hold the launches' records: free it after fwgpu_finish, and use it with one trainer at a time.
+ * fwgpu_text_parser_last_wait_ns: how long the host waited for the parser's stream during the last such call. */
+int fwgpu_trainer_digest_text_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, fwgpu_cache *cache, const char *text, uint64_t len,
+                                     uint64_t *n_examples, uint64_t *consumed);
+int fwgpu_trainer_digest_file_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, fwgpu_cache *cache, const char *filename,
+                                     uint64_t *n_examples);
+int fwgpu_text_parser_last_wait_ns(const fwgpu_text_parser *tp, uint64_t *ns);
+/* The micro-batch plan of that route (textparse.hip text_batch_plan) on host arrays, for tests.  status4: nlines x {status, record length, LR
+ * entries, FFM entries}, status (low byte) 1 = parsed by the device, 2 = needs the host, 3 = done by the host; a line of status 2 counts with
+ * zeros.  The first n_take lines are cut into windows of at most micro_batch lines, none of which straddles line learn_before_holdout
+ * (0xffffffff: no boundary).  Out: dst_off[n_take] and rec_off[n_take + 1] (word offsets), *n_windows, window_stats[7 per window] = examples,
+ * words, max_lr, max_ffm, max_rec, tot_lr, tot_ffm, and the status-2 lines of all nlines in order (host_lines[nlines], *n_host_lines). */
+int fwgpu_debug_text_plan(const uint32_t *status4, uint32_t nlines, uint32_t n_take, uint32_t micro_batch, uint32_t learn_before_holdout,
+                          uint64_t *dst_off, uint64_t *rec_off, uint32_t *n_windows, uint64_t *window_stats, uint32_t *host_lines,
+                          uint32_t *n_host_lines, void *stream);
 
 /* ---------------------------------------------------------------- model files
  * File = "FWRE", u32 version 6, u64 + JSON(vw_source), u64 + JSON(ModelInstance), weights blob (persistence.rs:17-97,
