@@ -28,6 +28,7 @@
 // plain cached loads.
 #include "fwgpu_internal.h"
 #include "fwgpu_device.h"
+#include "wave_balance.h"
 #include <cstdlib>
 #include <cstddef>
 #include <algorithm>
@@ -2748,6 +2749,9 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #ifndef FW_UO  // overflow rows (w + acc) in flight per wave in the update (2 / 4 / 5 against 1 with the deep head: profiles/r06_configE_v2_head.txt; headless k = 16: profiles/r05_k16_overflow_rows_in_flight_ab.txt)
 #define FW_UO 1
 #endif
+#ifndef FW_OWNER_MID  // config-C kernel: a wave's range ends on the field boundary NEAREST to w nf / nw (1) instead of the first one at or behind it (0) (profiles/r07_wave_balance.txt)
+#define FW_OWNER_MID 1
+#endif
 #ifndef FW_PIPE_DEPTH  // rows the accumulator loads of the pipelined kept-row update run ahead, at most (profiles/r04_pipeline_depth_ab.txt)
 #define FW_PIPE_DEPTH 3
 #endif
@@ -2861,8 +2865,18 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         tk_last = now_;                                               \
     }
     if (timing) tk_last = __builtin_amdgcn_s_memtime();
+    // ... and EVERY wave's wait at the two barriers its rows end on: slot 12 = behind the gather, slot 13 = at the loop top (from the end of its update),
+    // slot 14 = the wave's whole example (loop top to loop top); summed over the waves, so slot 12 / slot 14 is the share of wave-time spent waiting
+    const bool timing_w = p.ticks != nullptr && (tid & 63) == 0;
+    unsigned long long tw_top = 0, tw_mark = 0;
+#define FW_WAVE_MARK() \
+    if (timing_w) tw_mark = __builtin_amdgcn_s_memtime();
+#define FW_WAVE_WAITED(slot) \
+    if (timing_w) atomicAdd(p.ticks + (slot), __builtin_amdgcn_s_memtime() - tw_mark);
 #else
 #define FW_TICK(slot)
+#define FW_WAVE_MARK()
+#define FW_WAVE_WAITED(slot)
 #endif
 
     if (tid == 0) {
@@ -2897,6 +2911,16 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             bind_lds(p, smem, use_lut, s, geom, trl);
             if (grid_now == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // in-order mode: see fw_example_kernel
             __syncthreads();
+#ifdef FW_TICKS
+            if (timing_w) {
+                const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+                if (tw_top) {
+                    atomicAdd(p.ticks + 13, now_ - tw_mark);
+                    atomicAdd(p.ticks + 14, now_ - tw_top);
+                }
+                tw_top = now_;
+            }
+#endif
             ex = s.ctr[6];
             if (ex >= p.n_examples) break;
             FW_TICK(6);
@@ -2941,10 +2965,12 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         FW_TICK(1);
 
         // ---------------- this wave's feature range [lo, hi): the fields f with floor(fstart[f]*nw/nf) == wave
+        // (config-C kernel: the fields whose MIDDLE lies in the wave's share -- wave_of_field: the ranges end on the nearest field boundary, not on the next one)
+        constexpr bool kOwnerMid = WIN && NC == 1 && MAXR > 0 && FW_OWNER_MID;
         uint32_t lo = 0xffffffffu, hi = 0;
         for (uint32_t f = lane; f < F; f += 64) {
             const uint32_t a = s.fstart[f], b = s.fend[f];
-            if (b > a && (a * (uint32_t)nw) / nf == (uint32_t)wave) {
+            if (b > a && (kOwnerMid ? wave_of_field(a, b, (uint32_t)nw, nf) : (a * (uint32_t)nw) / nf) == (uint32_t)wave) {
                 lo = a < lo ? a : lo;
                 hi = b > hi ? b : hi;
             }
@@ -3117,7 +3143,9 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             }
 #undef FW_CONSUME
         }
+        FW_WAVE_MARK();
         __syncthreads();
+        FW_WAVE_WAITED(12);
         FW_TICK(2);
         // ---------------- the NEXT example's record: HBM -> registers now, -> LDS after the dot phase.  Its stage phase then needs no memory
         // round trip, so the acknowledgements of this example's row stores are waited for under the next stage phase's LDS work, not before it.
@@ -3488,6 +3516,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             }
             FW_TICK(5);
         }
+        FW_WAVE_MARK();
         // (the tail's lane tests start from a fresh thread index: `tid == 0` from the top of the example would be one more mask alive across the whole body)
         int tid_tail = FW_TID_FRESH();
         asm volatile("; thread index handed out" : "+v"(tid_tail));
@@ -3517,6 +3546,8 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         }
     }
 #undef FW_TICK
+#undef FW_WAVE_MARK
+#undef FW_WAVE_WAITED
 #undef FW_TID_FRESH
 }
 
