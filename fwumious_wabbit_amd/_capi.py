@@ -24,6 +24,9 @@ MODE_SEQUENTIAL, MODE_HOGWILD = 0, 1
 TABLE_LR, TABLE_FFM_W, TABLE_FFM_ACC, TABLE_NN_W, TABLE_NN_ACC = 0, 1, 2, 3, 4
 # fwgpu_debug_last_route
 ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK = 0, 1, 2, 3, 4, 5
+# fwgpu_debug_last_launch
+KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED = 0, 1, 2, 3
+LAUNCH_INFO = ("family", "chunks", "window", "chain", "no_kept_rows", "lds_keep", "threads", "lds_bytes")
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
 CANDIDATE_INFO = np.dtype([("code", "<i4"), ("is_delta", "u1"), ("record_ok", "u1"), ("by_host", "u1"), ("pad", "u1"), ("n_lr", "<u4"),
@@ -201,6 +204,7 @@ def lib():
         "fwgpu_debug_set_kernel_version": [vp, i32],
         "fwgpu_debug_set_option": [vp, i32, i32],
         "fwgpu_debug_last_route": [vp, P(i32)],
+        "fwgpu_debug_last_launch": [vp, P(i32), u32],
         "fwgpu_debug_head_inputs": [vp, vp, u64],
         "fwgpu_debug_coherence_probe": [i32, i32, u32, P(u32), P(u32)],
         "fwgpu_debug_head_gemm": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp],

@@ -263,6 +263,7 @@ struct LaunchConfig {
 
 size_t example_kernel_lds_bytes(const KernelParams &p, int optimizer);
 bool example_kernel_is_resident(const KernelParams &p, uint32_t threads);  // does a launch of this shape run on the v2 kernel (fw_example_kernel_r)?
+int example_kernel_family(const KernelParams &p, uint32_t threads);  // FWGPU_KERNEL_SCALAR / _VEC4 / _RESIDENT: the kernel launch_example_kernel picks for this shape
 void resolve_row_mode(KernelParams &p, uint32_t threads);  // settles KernelParams::window / chain for this launch shape
 // Enqueue the example kernel.  grid==1 gives the sequential (in-order) semantics.
 hipError_t launch_example_kernel(const KernelParams &p, int optimizer, bool coherent, uint32_t grid,
@@ -412,6 +413,7 @@ struct fwgpu_regressor {
     uint32_t pred_cap = 0;
     uint32_t pred_n = 0;                   // examples whose x the last batched predict launch left in pred_x (0: the last batch launch took another route)
     int32_t last_route = 0;                // FWGPU_ROUTE_* of the last fwgpu_learn_batch (fwgpu_debug_last_route)
+    int32_t last_launch[8] = {-1, 0, 0, 0, 0, 0, 0, 0};  // the resolved shape of the last example-kernel launch (fwgpu_debug_last_launch)
     // scratch for single-example calls
     fwgpu_batch *one = nullptr;
     void *pinned = nullptr;

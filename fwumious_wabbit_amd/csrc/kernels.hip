@@ -3621,23 +3621,30 @@ void resolve_row_mode(KernelParams &p, uint32_t threads) {
     p.lds_keep_words = p.lds_keep * (threads / 64) * p.R;
 }
 
+// Which kernel a launch of this shape runs on (launch_example_kernel dispatches on it; fwgpu_debug_last_launch reports it).
+// 16-byte row vectors need k % 4 == 0: then R % 4 == 0 and hash & mask is a multiple of next_pow2(k) >= 4
+// floats (feature_buffer.rs:141-148), so every row starts 16-byte aligned.
+// Entries that did not come through the translator's mask (raw fwgpu_learn calls) may be unaligned.
+int example_kernel_family(const KernelParams &p, uint32_t threads) {
+    if (p.k % 4 == 0 && p.aligned4) {
+        // single-chunk rows: the register-resident kernel (v2); p.kernel_version == 1 forces v1 (tests, A/B runs)
+        return uses_resident_kernel(p, threads) ? FWGPU_KERNEL_RESIDENT : FWGPU_KERNEL_VEC4;
+    }
+    return FWGPU_KERNEL_SCALAR;
+}
+
 hipError_t launch_example_kernel(const KernelParams &p_in, int optimizer, bool coherent, uint32_t grid, uint32_t threads,
                                  hipStream_t stream) {
     if (p_in.n_examples == 0 && !p_in.host_extra_wgs) return hipSuccess;
     KernelParams p = p_in;
-    const bool v2 = uses_resident_kernel(p, threads);
+    const int family = example_kernel_family(p, threads);
     resolve_row_mode(p, threads);  // (idempotent: run_batch has normally done it already, to size the LDS)
-    (void)v2;
     const size_t lds = example_kernel_lds_bytes(p, optimizer);
-    // 16-byte row vectors need k % 4 == 0: then R % 4 == 0 and hash & mask is a multiple of next_pow2(k) >= 4
-    // floats (feature_buffer.rs:141-148), so every row starts 16-byte aligned.
-    // Entries that did not come through the translator's mask (raw fwgpu_learn calls) may be unaligned.
-    if (p.k % 4 == 0 && p.aligned4) {
-        // single-chunk rows: the register-resident kernel (v2); p.kernel_version == 1 forces v1 (tests, A/B runs)
-        if (v2) return launch_resident(p, optimizer, coherent, grid, threads, lds, stream);
-        return launch_v<4>(p, optimizer, coherent, grid, threads, lds, stream);
+    switch (family) {
+    case FWGPU_KERNEL_RESIDENT: return launch_resident(p, optimizer, coherent, grid, threads, lds, stream);
+    case FWGPU_KERNEL_VEC4: return launch_v<4>(p, optimizer, coherent, grid, threads, lds, stream);
+    default: return launch_v<1>(p, optimizer, coherent, grid, threads, lds, stream);
     }
-    return launch_v<1>(p, optimizer, coherent, grid, threads, lds, stream);
 }
 
 // ------------------------------------------------------------------ packed FFM table (fwgpu_model_load_packed)

@@ -519,6 +519,21 @@ static int prepare_launch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int upda
     return FWGPU_OK;
 }
 
+// what fwgpu_debug_last_launch reports: the RESOLVED parameters of an example-kernel launch (after prepare_launch / resolve_row_mode)
+static void record_launch(fwgpu_regressor *r, const KernelParams &p, uint32_t threads, bool packed, int optimizer) {
+    const int family = packed ? FWGPU_KERNEL_PACKED : example_kernel_family(p, threads);
+    const uint32_t per_chunk = family == FWGPU_KERNEL_SCALAR ? 64u : 256u;  // floats of a row that one pass of a wave covers (1 or 4 per lane)
+    r->last_launch[0] = family;
+    r->last_launch[1] = (int32_t)((p.R + per_chunk - 1) / per_chunk);
+    // (the packed kernel is predict-only and sizes its LDS inside launch_packed_predict: the update path's fields and the LDS size are not reported for it)
+    r->last_launch[2] = packed ? 0 : p.window;
+    r->last_launch[3] = packed ? 0 : p.chain;
+    r->last_launch[4] = packed ? 0 : p.no_kept_rows;
+    r->last_launch[5] = packed ? 0 : (int32_t)p.lds_keep;
+    r->last_launch[6] = (int32_t)threads;
+    r->last_launch[7] = packed ? 0 : (int32_t)example_kernel_lds_bytes(p, optimizer);
+}
+
 static int run_batch_by_example(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream);
 static bool head_predict_batched(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update);
 static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_t stream);
@@ -546,6 +561,7 @@ static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int up
     } else {
         FWGPU_HIP(hipMemsetAsync(b->work, 0, sizeof(uint32_t), stream));
     }
+    record_launch(r, p, threads, true, FWGPU_OPT_SGD);
     FWGPU_HIP(launch_packed_predict(p, r->q_increment, r->q_min, grid, threads, stream));
     return FWGPU_OK;
 }
@@ -580,6 +596,7 @@ static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, h
         FWGPU_HIP(hipMemsetAsync(b->work, 0, sizeof(uint32_t), stream));
     }
     // An updating launch always uses device-scope (sc1) accesses; read-only launches use cached loads.
+    record_launch(r, p, threads, false, r->cfg.optimizer);
     FWGPU_HIP(launch_example_kernel(p, r->cfg.optimizer, update != 0, grid, threads, stream));
     return FWGPU_OK;
 }
@@ -633,6 +650,7 @@ static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_
     } else {
         FWGPU_HIP(hipMemsetAsync(b->work, 0, sizeof(uint32_t), stream));
     }
+    record_launch(r, p, threads, false, r->cfg.optimizer);
     FWGPU_HIP(launch_example_kernel(p, r->cfg.optimizer, false, 0, threads, stream));
     fwgpu_split view;
     view.owner = r;
@@ -666,6 +684,7 @@ int run_batch_peer(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, con
     p.host_stream_min_consumer_waves = (d_push && stream_consumers) ? 2u * (n_ranks ? n_ranks : 1u) : 0u;
     const uint32_t grid = pick_grid(r, p, mode, threads);
     FWGPU_HIP(hipMemsetAsync(b->work, 0, sizeof(uint32_t), stream));
+    record_launch(r, p, threads, false, r->cfg.optimizer);
     FWGPU_HIP(launch_example_kernel(p, r->cfg.optimizer, update != 0, grid, threads, stream));
     return FWGPU_OK;
 }
@@ -1722,6 +1741,13 @@ int fwgpu_learn_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, 
 int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route) {
     if (!r || !route) return fail(FWGPU_ERR_INVALID, "NULL argument");
     *route = r->last_route;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n) {
+    if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (n > FWGPU_LAUNCH_INFO_LEN) return fail(FWGPU_ERR_RANGE, "last_launch: more fields than the library fills (FWGPU_LAUNCH_INFO_LEN)");
+    for (uint32_t i = 0; i < n; i++) out[i] = r->last_launch[i];
     return FWGPU_OK;
 }
 

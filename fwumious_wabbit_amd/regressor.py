@@ -448,6 +448,13 @@ class Regressor:
         check(self.L.fwgpu_debug_last_route(self.h, C.byref(route)))
         return route.value
 
+    def last_launch(self):
+        """what this regressor's last example-kernel launch ran, from its resolved parameters: a dict of capi.LAUNCH_INFO -- family (capi.KERNEL_*;
+        -1 before the first launch), chunks per row, window, chain, no_kept_rows, lds_keep, threads, lds_bytes (fwgpu_debug_last_launch)"""
+        out = (C.c_int32 * len(capi.LAUNCH_INFO))()
+        check(self.L.fwgpu_debug_last_launch(self.h, out, len(capi.LAUNCH_INFO)))
+        return dict(zip(capi.LAUNCH_INFO, (int(x) for x in out)))
+
     def head_inputs(self, n):
         """the head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] of the first n examples of the last batched head predict launch, as an
         (n, X) float32 array; an error if the last learn_batch took another route (fwgpu_debug_head_inputs)"""

@@ -488,6 +488,20 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value);
 #define FWGPU_ROUTE_PACKED 4               /* packed regressor: the packed predict kernel (or its refusal) */
 #define FWGPU_ROUTE_HOST_WALK 5            /* a batch with an oversize example: walked example by example from its host copy */
 int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
+/* What the regressor's last example-kernel launch ran, from its RESOLVED launch parameters (host side, read-only; every batch launch that reaches the
+ * example kernel records it, the launch of a refused batch does not): the first n <= FWGPU_LAUNCH_INFO_LEN of
+ *   [0] kernel family (FWGPU_KERNEL_*; -1: no launch yet)   [1] chunks per row: ceil(R / 64) on the scalar kernel, ceil(R / 256) on the 16-byte kernels
+ *   [2] window (the chained whole-row update path)          [3] chain (duplicate rows chained to their first occurrence)
+ *   [4] no_kept_rows (option 13 = 0)                        [5] lds_keep (rows per wave parked in LDS, after clamping)
+ *   [6] threads per workgroup                               [7] LDS bytes per workgroup
+ * FWGPU_KERNEL_PACKED: [0], [1] and [6] as above ([1]: ceil(R / 256), the packed kernel's one or two chunks); [2]..[5] describe update paths a
+ * predict-only kernel does not have and are 0; [7] is 0 (the packed launch sizes its LDS itself, it is not reported). */
+#define FWGPU_KERNEL_SCALAR 0   /* generic kernel, one float per lane (k % 4 != 0, or an entry batch with a row off a 16-byte boundary) */
+#define FWGPU_KERNEL_VEC4 1     /* generic kernel, 16 bytes per lane */
+#define FWGPU_KERNEL_RESIDENT 2 /* register-resident kernel (rows of up to 256 floats, or up to 512 where 256 % k == 0) */
+#define FWGPU_KERNEL_PACKED 3   /* ... its predict-only instantiation on a packed table */
+#define FWGPU_LAUNCH_INFO_LEN 8
+int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
  * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED,
  * FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */

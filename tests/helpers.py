@@ -2,7 +2,10 @@
 import numpy as np
 
 import fwumious_wabbit_amd as fw
+from fwumious_wabbit_amd import _capi as capi
 from oracle import fwo
+
+LOGLOSS_TOL = 1e-4   # north_star: per-example log-loss tolerance
 
 
 def mi_from_cfg(d, wiring="regressor", n_fields=None):
@@ -59,6 +62,55 @@ def logloss(p, y):
 
 def record_labels(records, rec_off):
     return np.array([records[int(o) + 1] for o in rec_off[:-1]], dtype=np.float32)
+
+
+# ------------------------------------------------------------------ streams: sequential mode == reference single thread
+def _stream_parity(n_ns, k, bits, ffm_bits, optimizer, n, mean_extra, p_weighted, ids, seed, interactions=(),
+                   weight_tol=2e-5, whole_lines=None, lds_keep=None, kept_rows=None, launches=None, **kw):
+    """(`launches`: a list that receives Regressor.last_launch() of the entries' and of the records' launch)"""
+    mi, ocfg, ots = make_pair(n_ns, k, bits, ffm_bits, optimizer, interactions=interactions, **kw)
+    recs, off = fw.synth_records(n_ns, mean_extra, 1.1, ids, p_weighted, seed, 0, n)
+    y = record_labels(recs, off)
+    om = fwo.Model(ocfg)
+    _, p_ref = om.run_stream(ots, recs, off, holdout_after=0, nthreads=1)
+    results = []
+    # both ways of feeding the device: entries translated on the host, and raw records translated inside the kernel
+    for kind in ("entries", "records"):
+        re = fw.Regressor(mi)
+        if whole_lines is not None:
+            re.set_whole_line_updates(whole_lines)
+        if lds_keep is not None:
+            re.set_lds_keep(lds_keep)
+        if kept_rows is not None:
+            re.set_kept_rows(kept_rows)
+        fbt = fw.FeatureBufferTranslator(mi)
+        b = re.batch_from_records(fbt, recs, off) if kind == "entries" else re.record_batch(fbt, recs, off)
+        re.learn_batch(b, capi.MODE_SEQUENTIAL, True)
+        if launches is not None:
+            launches.append(re.last_launch())
+        p_gpu = b.predictions()
+        d_ll = np.abs(logloss(p_gpu, y) - logloss(p_ref, y))
+        assert d_ll.max() < LOGLOSS_TOL, f"{kind}: max per-example |d logloss| = {d_ll.max()} at {d_ll.argmax()}"
+        assert np.abs(p_gpu - p_ref).max() < 5e-5
+        # final tables: same state as the reference after the whole stream
+        # (weights are O(0.1); accumulators grow to O(100), hence the relative term)
+        def close(a, b_):
+            return bool(np.all(np.abs(a - b_) <= weight_tol + 1e-5 * np.abs(b_)))
+
+        assert close(re.table_read(capi.TABLE_LR), om.lr_table)
+        if k:
+            assert close(re.table_read(capi.TABLE_FFM_W), om.ffm_weights)
+            acc_g, acc_o = re.table_read(capi.TABLE_FFM_ACC), om.ffm_acc
+            assert close(acc_g, acc_o)
+            # exactly the same set of accumulators was touched
+            a0 = np.float32(mi.ffm_init_acc_gradient if optimizer == fw.Optimizer.AdagradFlex else 0.0)
+            assert np.array_equal(acc_g != a0, acc_o != a0)
+        results.append((p_gpu, [re.table_checksum(t) for t in (capi.TABLE_LR, capi.TABLE_FFM_W, capi.TABLE_FFM_ACC)]))
+        b.close()
+        re.close()
+    # device-side translation == host translation, bit for bit (hash indices and everything downstream)
+    assert np.array_equal(results[0][0], results[1][0]) and results[0][1] == results[1][1]
+    return results[0][0], p_ref
 
 
 # ------------------------------------------------------------------ streams whose examples share nothing

@@ -25,7 +25,7 @@ from oracle import fwo
 
 pytestmark = pytest.mark.gpu
 
-LOGLOSS_TOL = 1e-4  # as test_gpu_parity._stream_parity
+LOGLOSS_TOL = 1e-4  # as helpers._stream_parity
 LUT, FLEX, SGD = fw.Optimizer.AdagradLUT, fw.Optimizer.AdagradFlex, fw.Optimizer.SGD
 TABLES = (capi.TABLE_LR, capi.TABLE_FFM_W, capi.TABLE_FFM_ACC)
 _NAMES = {capi.TABLE_LR: "LR", capi.TABLE_FFM_W: "FFM_W", capi.TABLE_FFM_ACC: "FFM_ACC", capi.TABLE_NN_W: "NN_W"}

@@ -80,6 +80,8 @@ def _launch(re, b, want_route, batched=1):
     re.learn_batch(b, capi.MODE_HOGWILD, False)
     route = re.last_route()
     assert route == want_route, f"route: {ROUTE_NAME[route]}, expected {ROUTE_NAME[want_route]}"
+    if route == capi.ROUTE_HEAD_BATCHED:  # (the head inputs come from the register-resident kernel's read-only launch)
+        assert re.last_launch()["family"] == capi.KERNEL_RESIDENT
     return b.predictions().copy()
 
 

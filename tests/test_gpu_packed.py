@@ -171,6 +171,7 @@ def test_packed_predictions_match_the_oracle_on_the_weights_the_buckets_stand_fo
         bf = rf.batch_from_records(fbt, recs, off) if kind == "entries" else rf.record_batch(fbt, recs, off)
         for mode in (capi.MODE_HOGWILD, capi.MODE_SEQUENTIAL):
             rp.learn_batch(b, mode, False)
+            assert rp.last_launch()["family"] == capi.KERNEL_PACKED
             p = b.predictions().copy()
             print(f"{kind} mode {mode}: max |p_packed - p_oracle| = {np.abs(p - p_ref).max():.3e}, "
                   f"max |d logloss| = {np.abs(logloss(p, y) - logloss(p_ref, y)).max():.3e}")
@@ -179,6 +180,7 @@ def test_packed_predictions_match_the_oracle_on_the_weights_the_buckets_stand_fo
             rp.learn_batch(b, mode, False)
             assert np.array_equal(b.predictions(), p)  # two identical launches
             rf.learn_batch(bf, mode, False)
+            assert rf.last_launch()["family"] == capi.KERNEL_RESIDENT
             pf = bf.predictions().copy()
             assert np.abs(p - pf).max() < PRED_TOL   # the f32 load of the same quantised model
             bit_equal = bit_equal and np.array_equal(p, pf)

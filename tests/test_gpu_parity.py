@@ -13,7 +13,7 @@ import pytest
 
 import fwumious_wabbit_amd as fw
 from fwumious_wabbit_amd import _capi as capi
-from helpers import logloss, make_pair, mi_from_cfg, record_labels
+from helpers import _stream_parity, logloss, make_pair, mi_from_cfg, record_labels
 from oracle import fwo
 
 pytestmark = pytest.mark.gpu
@@ -52,49 +52,7 @@ def test_smoke_entry():
 
 
 # ------------------------------------------------------------------ streams: sequential mode == reference single thread
-def _stream_parity(n_ns, k, bits, ffm_bits, optimizer, n, mean_extra, p_weighted, ids, seed, interactions=(),
-                   weight_tol=2e-5, whole_lines=None, lds_keep=None, kept_rows=None, **kw):
-    mi, ocfg, ots = make_pair(n_ns, k, bits, ffm_bits, optimizer, interactions=interactions, **kw)
-    recs, off = fw.synth_records(n_ns, mean_extra, 1.1, ids, p_weighted, seed, 0, n)
-    y = record_labels(recs, off)
-    om = fwo.Model(ocfg)
-    _, p_ref = om.run_stream(ots, recs, off, holdout_after=0, nthreads=1)
-    results = []
-    # both ways of feeding the device: entries translated on the host, and raw records translated inside the kernel
-    for kind in ("entries", "records"):
-        re = fw.Regressor(mi)
-        if whole_lines is not None:
-            re.set_whole_line_updates(whole_lines)
-        if lds_keep is not None:
-            re.set_lds_keep(lds_keep)
-        if kept_rows is not None:
-            re.set_kept_rows(kept_rows)
-        fbt = fw.FeatureBufferTranslator(mi)
-        b = re.batch_from_records(fbt, recs, off) if kind == "entries" else re.record_batch(fbt, recs, off)
-        re.learn_batch(b, capi.MODE_SEQUENTIAL, True)
-        p_gpu = b.predictions()
-        d_ll = np.abs(logloss(p_gpu, y) - logloss(p_ref, y))
-        assert d_ll.max() < LOGLOSS_TOL, f"{kind}: max per-example |d logloss| = {d_ll.max()} at {d_ll.argmax()}"
-        assert np.abs(p_gpu - p_ref).max() < 5e-5
-        # final tables: same state as the reference after the whole stream
-        # (weights are O(0.1); accumulators grow to O(100), hence the relative term)
-        def close(a, b_):
-            return bool(np.all(np.abs(a - b_) <= weight_tol + 1e-5 * np.abs(b_)))
-
-        assert close(re.table_read(capi.TABLE_LR), om.lr_table)
-        if k:
-            assert close(re.table_read(capi.TABLE_FFM_W), om.ffm_weights)
-            acc_g, acc_o = re.table_read(capi.TABLE_FFM_ACC), om.ffm_acc
-            assert close(acc_g, acc_o)
-            # exactly the same set of accumulators was touched
-            a0 = np.float32(mi.ffm_init_acc_gradient if optimizer == fw.Optimizer.AdagradFlex else 0.0)
-            assert np.array_equal(acc_g != a0, acc_o != a0)
-        results.append((p_gpu, [re.table_checksum(t) for t in (capi.TABLE_LR, capi.TABLE_FFM_W, capi.TABLE_FFM_ACC)]))
-        b.close()
-        re.close()
-    # device-side translation == host translation, bit for bit (hash indices and everything downstream)
-    assert np.array_equal(results[0][0], results[1][0]) and results[0][1] == results[1][1]
-    return results[0][0], p_ref
+# (_stream_parity: helpers.py -- tests/test_gpu_ffm_step.py runs the never-run kernel shapes through it too)
 
 
 def test_sequential_stream_config_b_like_with_collisions():
