@@ -2719,6 +2719,13 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return v;
 }
 
+// Split fields (FW_SPLIT_FIELDS, wave_balance.h): the rows at the front of the range that starts at row lo which belong to a field begun in front of
+// it -- the range's lead; 0 where the range starts on a field boundary.  Wave-uniform, from the staged example alone.
+__device__ __forceinline__ uint32_t split_lead(const Lds &s, uint32_t lo) {
+    const uint32_t f = __builtin_amdgcn_readfirstlane(s.e_fld[lo]) & kFldMask;
+    return __builtin_amdgcn_readfirstlane(s.fstart[f]) < lo ? __builtin_amdgcn_readfirstlane(s.fend[f]) - lo : 0u;
+}
+
 // Build-time knobs of the v2 kernel and its launchers: plain numbers, each overridable with -DFW_...=N (scripts/build_variant.sh).
 // The alternatives that were code paths (keep-last, through-register parking, strided adds, ...) are gone: profiles/HISTORY.md, "Build switches removed".
 //
@@ -2751,6 +2758,12 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #endif
 #ifndef FW_OWNER_MID  // config-C kernel: a wave's range ends on the field boundary NEAREST to w nf / nw (1) instead of the first one at or behind it (0) (profiles/r07_wave_balance.txt)
 #define FW_OWNER_MID 1
+#endif
+#ifndef FW_SPLIT_FIELDS  // config-C kernel: a wave's range starts at row w nf / nw even INSIDE a field (1: wave_balance.h split_cut, a second pass of the gather adds the cut field's lead rows in buffer order) or on a field boundary only (0) (profiles/r08_field_split.txt)
+#define FW_SPLIT_FIELDS 1
+#endif
+#ifndef FW_SPLIT_LEAD_MAX  // rows of a cut field that may fall into the second wave's range, at most (<= FW_MAXR_WIN: they are among its register-kept rows)
+#define FW_SPLIT_LEAD_MAX 8
 #endif
 #ifndef FW_PIPE_DEPTH  // rows the accumulator loads of the pipelined kept-row update run ahead, at most (profiles/r04_pipeline_depth_ab.txt)
 #define FW_PIPE_DEPTH 3
@@ -2967,16 +2980,34 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
         // ---------------- this wave's feature range [lo, hi): the fields f with floor(fstart[f]*nw/nf) == wave
         // (config-C kernel: the fields whose MIDDLE lies in the wave's share -- wave_of_field: the ranges end on the nearest field boundary, not on the next one)
         constexpr bool kOwnerMid = WIN && NC == 1 && MAXR > 0 && FW_OWNER_MID;
+        // (... and, FW_SPLIT_FIELDS, examples of at least 16 nw rows -- split_fields_on: [floor(w nf / nw), floor((w + 1) nf / nw)) even where that cuts a field in two -- split_cut;
+        // the field that holds a row is the row's own e_fld word, so a cut is a handful of wave-uniform LDS reads.  The first rows of a range that belong to
+        // a field begun by the wave before -- the LEAD, at most FW_SPLIT_LEAD_MAX -- are left out of the gather's first pass and added in a second one below.)
+        constexpr bool kSplit = kOwnerMid && FW_SPLIT_FIELDS;
+        static_assert(!kSplit || FW_SPLIT_LEAD_MAX <= MAXR, "a wave's lead rows are among its register-kept rows");
         uint32_t lo = 0xffffffffu, hi = 0;
-        for (uint32_t f = lane; f < F; f += 64) {
-            const uint32_t a = s.fstart[f], b = s.fend[f];
-            if (b > a && (kOwnerMid ? wave_of_field(a, b, (uint32_t)nw, nf) : (a * (uint32_t)nw) / nf) == (uint32_t)wave) {
-                lo = a < lo ? a : lo;
-                hi = b > hi ? b : hi;
+        if (kSplit && split_fields_on((uint32_t)nw, nf)) {
+            const uint32_t w_u = __builtin_amdgcn_readfirstlane((uint32_t)wave), nw_u = (uint32_t)nw;
+            auto cut = [&](uint32_t w) -> uint32_t {
+                if (w == 0u) return 0u;
+                if (w >= nw_u) return nf;
+                const uint32_t f = __builtin_amdgcn_readfirstlane(s.e_fld[(w * nf) / nw_u]) & kFldMask;
+                return split_cut(__builtin_amdgcn_readfirstlane(s.fstart[f]), __builtin_amdgcn_readfirstlane(s.fend[f]), w, nw_u, nf, (uint32_t)FW_SPLIT_LEAD_MAX);
+            };
+            lo = cut(w_u);
+            hi = cut(w_u + 1u);
+            if (hi <= lo) hi = 0;  // (an empty range, as below)
+        } else {
+            for (uint32_t f = lane; f < F; f += 64) {
+                const uint32_t a = s.fstart[f], b = s.fend[f];
+                if (b > a && (kOwnerMid ? wave_of_field(a, b, (uint32_t)nw, nf) : (a * (uint32_t)nw) / nf) == (uint32_t)wave) {
+                    lo = a < lo ? a : lo;
+                    hi = b > hi ? b : hi;
+                }
             }
+            lo = wave_min_u32(lo);
+            hi = wave_max_u32(hi);
         }
-        lo = wave_min_u32(lo);
-        hi = wave_max_u32(hi);
         // uniform by construction; saying so keeps the range and everything indexed by it in SGPRs, which removed the
         // kernel's VGPR spills (measured: 4.53 -> 4.29 ms per launch)
         lo = __builtin_amdgcn_readfirstlane(lo);
@@ -3066,6 +3097,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             }                                                                                                 \
             dc = 0.0f;                                                                                        \
             cur = f_;                                                                                         \
+            if (kSplit) asm volatile("; field handed out" : "+s"(cur)); /* (kept scalar: see below) */          \
         }                                                                                                     \
         _Pragma("unroll") for (int c = 0; c < NC; ++c) {                                                      \
             float ss_ = 0.0f;                                                                                 \
@@ -3080,13 +3112,22 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             }                                                                                                 \
         }                                                                                                     \
     }
+            // (split fields: FW_CONSUME hands the current field out through an empty asm.  Left alone, the compiler replaces it by the lane's own z in the lanes where
+            // the two are equal: `cur` becomes a vector register and every field switch a lane-masked block -- the register the second pass needs.)
             // (the count is handed out afresh: compared with the SAME value as in the burst above, every slot's `sl < nk` is computed once, up there,
             // and kept as a 64-bit lane mask until its row is consumed -- two scalar registers per kept row)
             uint32_t nk_c = __builtin_amdgcn_readfirstlane(nk);
             asm volatile("; kept-row count handed out" : "+s"(nk_c));
+            // (split fields: the wave's lead rows wait in rows[] for the second pass; a range that starts on a field boundary -- every range of a short
+            // example -- has none)
+            uint32_t lead_c = 0;
+            if (kSplit) {
+                lead_c = cnt ? split_lead(s, lo) : 0u;
+                asm volatile("; lead-row count handed out" : "+s"(lead_c));
+            }
 #pragma unroll
             for (int sl = 0; sl < MAXR; ++sl)
-                if ((uint32_t)sl < nk_c) {
+                if ((uint32_t)sl < nk_c && !(kSplit && sl < FW_SPLIT_LEAD_MAX && (uint32_t)sl < lead_c)) {
                     V one[NC];
                     one[0] = rows[sl];
                     FW_CONSUME(one, lo + sl)
@@ -3137,15 +3178,63 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     if (inbc[c]) Vec<VEC>::lds_store(s.T + zc[c] * R + cur * k + kkc[c], acc[c]);
-                dc = wave_sum(dc);
-                if (!COH && p.ctx_dcf) dc += p.ctx_dcf[cur];
-                s.dcf[cur] = dc;
+                if (kSplit && __builtin_amdgcn_readfirstlane(s.fend[cur]) > hi) {
+                    // the field goes on in the next wave's range: its partial sum waits in T like a finished one, and the partial self-pair term of
+                    // the k / 4 lanes that hold the field's own slot waits, per lane, in the own-slot words of the first lead row -- row hi, which
+                    // nobody writes before the second pass consumes it
+                    if (z == cur) s.selfw[hi * k + kkc[0]] = dc;
+                } else {
+                    dc = wave_sum(dc);
+                    if (!COH && p.ctx_dcf) dc += p.ctx_dcf[cur];
+                    s.dcf[cur] = dc;
+                }
             }
 #undef FW_CONSUME
         }
         FW_WAVE_MARK();
         __syncthreads();
         FW_WAVE_WAITED(12);
+        if (kSplit) {
+            // ---------------- the gather's second pass: a wave whose range starts inside a field takes that field's sum up where the wave before left it
+            // and adds its lead rows, in buffer order, from the registers they have waited in.  Every wave of every example meets the barrier behind it.
+            uint32_t lead_c = cnt ? split_lead(s, lo) : 0u;
+            asm volatile("; lead-row count handed out" : "+s"(lead_c));
+            if (lead_c) {
+                const uint32_t cur = __builtin_amdgcn_readfirstlane(s.e_fld[lo]) & kFldMask;
+                // (the lane's place in a row is formed afresh, as the update's is: through the gather's own values this pass kept their addresses alive in vector registers)
+                int tid_p = FW_TID_FRESH();
+                asm volatile("; thread index handed out" : "+v"(tid_p));
+                const uint32_t e0_p = (uint32_t)(tid_p & 63) * VEC;
+                const bool inb_p = e0_p < R;
+                const uint32_t z_p = inb_p ? e0_p >> p.k_log2 : 0xfffffffeu, kk_p = inb_p ? e0_p & (k - 1u) : 0u;  // (the window path: k is a power of two)
+                V acc = Vec<VEC>::zero();
+                if (inb_p) acc = Vec<VEC>::lds_load(s.T + z_p * R + cur * k + kk_p);
+                float dc = 0.0f;
+                if (z_p == cur) dc = s.selfw[lo * k + kk_p];
+#pragma unroll
+                for (int sl = 0; sl < FW_SPLIT_LEAD_MAX && sl < MAXR; ++sl)
+                    if ((uint32_t)sl < lead_c) {  // FW_CONSUME's step for a row of the field `cur`
+                        const V row = rows[sl < MAXR ? sl : 0];
+                        const float v_ = s.e_val[lo + sl];
+                        float ss_ = 0.0f;
+#pragma unroll
+                        for (int j = 0; j < VEC; ++j) {
+                            acc[j] = __fadd_rn(acc[j], __fmul_rn(row[j], v_));  // block_ffm.rs:205
+                            ss_ += row[j] * row[j];
+                        }
+                        if (z_p == cur) {
+                            dc += ss_ * v_ * v_;
+                            Vec<VEC>::lds_store(s.selfw + (lo + sl) * k + kk_p, row);
+                        }
+                    }
+                if (inb_p) Vec<VEC>::lds_store(s.T + z_p * R + cur * k + kk_p, acc);
+                dc = wave_sum(dc);
+                s.dcf[cur] = dc;
+            }
+            FW_WAVE_MARK();
+            __syncthreads();
+            FW_WAVE_WAITED(12);
+        }
         FW_TICK(2);
         // ---------------- the NEXT example's record: HBM -> registers now, -> LDS after the dot phase.  Its stage phase then needs no memory
         // round trip, so the acknowledgements of this example's row stores are waited for under the next stage phase's LDS work, not before it.
