@@ -121,7 +121,7 @@ class DisjointStream:
     `row_count` (occurrences in its example) and `row_ffm` (False: an LR-only feature, which has no FFM row)."""
 
 
-def disjoint_stream(F, k, n, per_field=(1, 1), p_weighted=0.0, p_dup=0.0, seed=0, lr_only_ns=0, first_ffm=None, first_lr=None):
+def disjoint_stream(F, k, n, per_field=(1, 1), p_weighted=0.0, p_dup=0.0, seed=0, lr_only_ns=0, first_ffm=None, first_lr=None, scatter=1):
     """n examples over F namespaces (== FFM fields; k = 0: LR only) that share NO FFM row, no 128-byte line of a row and no LR entry, so the
     order in which they are learned cannot matter.  Per field `per_field` = (lo, hi) features (seeded numpy draw), a share `p_weighted` of them
     with a value other than 1, a share `p_dup` followed by the same feature once more in the same field (a chained duplicate row); labels
@@ -132,27 +132,31 @@ def disjoint_stream(F, k, n, per_field=(1, 1), p_weighted=0.0, p_dup=0.0, seed=0
     phase of a line occurs (where the translator's mask -- multiples of next_pow2(k) -- allows it) and rows of different examples are a line
     apart.  The raw hash IS that float index: with LR bits >= FFM bits and no interaction combos the LR indices differ like the rows.
     The models must be built with add_constant_feature = False (disjoint_models): the constant's entry would be shared by every example.
-    check_disjoint() asserts all of this on the host translator's output."""
+    check_disjoint() asserts all of this on the host translator's output.
+
+    `scatter` = m > 1 (a power of two): the 2^ffm_bits table is cut into m equal regions and row i goes into region i % m, (i // m) * S floats into
+    it (the phase 8 * (i % 4) as above), so an example's consecutive rows lie in different regions -- with owners taken from a hash's high bits
+    (multi-rank modes) at different owners -- and no row crosses a region's end.  The features are drawn first and the slots assigned afterwards:
+    values, labels, importances and duplicates are those of the scatter = 1 stream of the same seed.  `span` is then the whole table."""
     rng = np.random.default_rng(seed)
     R = F * k
     S = ((R + 64 + 31) // 32) * 32 if k else 1
     n_ns = F + lr_only_ns
-    ex, hsh, fld, val = [], [], [], []
-    row_hash, row_ex, row_count, row_ffm = [], [], [], []
-    recs, off = [], [0]
+    assert scatter >= 1 and scatter & (scatter - 1) == 0
+    row_ex, row_count, row_ffm = [], [], []
     vals = np.array([0.5, 2.0, 0.75, 1.5], dtype=np.float32)
+    drawn = []  # per example: (slots[ns] = [(row, value)], label, importance word)
     for e in range(n):
         slots = [[] for _ in range(n_ns)]
 
         def feature(ns, allow_dup=True):
-            i = len(row_hash)
-            h = i * S + (8 * (i % 4) if k and k % 4 == 0 else 0)
+            i = len(row_ex)
             c = 0
             for _ in range(2 if allow_dup and rng.random() < p_dup else 1):
                 v = float(vals[rng.integers(0, 4)]) if rng.random() < p_weighted else 1.0
-                slots[ns].append((h, v))
+                slots[ns].append((i, v))
                 c += 1
-            row_hash.append(h), row_ex.append(e), row_count.append(c), row_ffm.append(bool(k) and ns < F)
+            row_ex.append(e), row_count.append(c), row_ffm.append(bool(k) and ns < F)
 
         for ns in range(n_ns):
             for _ in range(int(rng.integers(per_field[0], per_field[1] + 1)) if ns < F else 1):
@@ -165,8 +169,26 @@ def disjoint_stream(F, k, n, per_field=(1, 1), p_weighted=0.0, p_dup=0.0, seed=0
             while sum(len(s) for s in slots) < first_lr:
                 feature(F, allow_dup=False)
             assert sum(len(s) for s in slots) == first_lr
-        rec = [0, int(rng.integers(0, 2)), int(np.float32(1.0 if rng.random() < 0.7 else 0.5).view(np.uint32))] + [0] * n_ns
+        drawn.append((slots, int(rng.integers(0, 2)), int(np.float32(1.0 if rng.random() < 0.7 else 0.5).view(np.uint32))))
+    # the slots: row i of the batch -> its first float
+    n_rows = len(row_ex)
+    per_region = (n_rows + scatter - 1) // scatter  # rows a region holds
+    span = n_rows * S if scatter == 1 else scatter * per_region * S
+    ffm_bits = max(10, int(np.ceil(np.log2(span))))  # the smallest table that holds the rows
+    assert ffm_bits <= 27, "drop n rather than exceed a 27-bit table"
+    region = (1 << ffm_bits) // scatter
+    assert per_region * S <= region
+    phase = 8 * (np.arange(n_rows) % 4) if k and k % 4 == 0 else 0
+    row_hash = ((np.arange(n_rows) % scatter) * region + (np.arange(n_rows) // scatter) * S + phase).astype(np.int64)
+    if scatter > 1:
+        assert not k or np.all(row_hash % region + R + 32 <= region), "a row (rounded to lines) crosses its region's end"
+        span = 1 << ffm_bits
+    ex, hsh, fld, val = [], [], [], []
+    recs, off = [], [0]
+    for e, (slots, label, imp) in enumerate(drawn):
+        rec = [0, label, imp] + [0] * n_ns
         for ns, s in enumerate(slots):
+            s = [(int(row_hash[i]), v) for i, v in s]
             for h, v in s:
                 ex.append(e), hsh.append(h), fld.append(ns if ns < F and k else -1), val.append(v)
             if len(s) == 1 and s[0][1] == 1.0:
@@ -181,16 +203,14 @@ def disjoint_stream(F, k, n, per_field=(1, 1), p_weighted=0.0, p_dup=0.0, seed=0
         recs += rec
         off.append(len(recs))
     st = DisjointStream()
-    st.F, st.k, st.n, st.R, st.S, st.n_ns, st.lr_only_ns = F, k, n, R, S, n_ns, lr_only_ns
+    st.F, st.k, st.n, st.R, st.S, st.n_ns, st.lr_only_ns, st.scatter = F, k, n, R, S, n_ns, lr_only_ns, scatter
     st.recs, st.off = np.array(recs, dtype=np.uint32), np.array(off, dtype=np.uint64)
     st.ex, st.hash, st.fld, st.val = np.array(ex), np.array(hsh, dtype=np.int64), np.array(fld), np.array(val, dtype=np.float32)
-    st.row_hash, st.row_ex = np.array(row_hash, dtype=np.int64), np.array(row_ex)
+    st.row_hash, st.row_ex = row_hash, np.array(row_ex)
     st.row_count, st.row_ffm = np.array(row_count), np.array(row_ffm, dtype=bool)
-    span = len(row_hash) * S  # floats of the FFM tables (LR entries) that the batch can touch: row i lies inside [i * S, (i + 1) * S)
-    st.ffm_bits = max(10, int(np.ceil(np.log2(span))))  # the smallest table that holds the rows
+    st.ffm_bits = ffm_bits
     st.bits = st.ffm_bits  # LR bits >= FFM bits: the LR index of a feature is its row's first float
-    assert st.ffm_bits <= 27, "drop n rather than exceed a 27-bit table"
-    st.span = span
+    st.span = span  # floats of the FFM tables (LR entries) that the batch can touch: row i lies inside [i * S, (i + 1) * S) (scatter > 1: the table)
     st.labels = record_labels(st.recs, st.off)
     st.fbs = None
     return st
@@ -214,7 +234,8 @@ def disjoint_models(st, optimizer, lr=0.1, ffm_lr=0.1, power_t=0.5, ffm_power_t=
 
 def check_disjoint(st, mi):
     """The condition the whole argument rests on, on the HOST TRANSLATOR's output (fbt.translate): the line-rounded intervals [h, h + R) of
-    different examples' FFM rows are pairwise disjoint (asserted on each example's envelope: an example's rows are neighbours in the table),
+    different examples' FFM rows are pairwise disjoint (asserted on each example's envelope: an example's rows are neighbours in the table;
+    scatter > 1: on every row's own interval, sorted and compared with its neighbour -- a row that two examples hold is two equal intervals),
     no LR hash occurs in two examples, and the translator's entries are the generator's own bookkeeping.  Fills st.fbs (the entry route)."""
     fbt = fw.FeatureBufferTranslator(mi)
     assert not mi.add_constant_feature
@@ -234,8 +255,13 @@ def check_disjoint(st, mi):
             assert np.array_equal(h, want_h[sel] & int(fbt.ffm_hash_mask)) and np.array_equal(fb.ffm_buffer["value"], want_v[sel]), e
             assert np.array_equal(fb.ffm_buffer["contra_field_index"], want_f[sel] * st.k), e
             assert h.max() + st.R <= (1 << st.ffm_bits) + st.R
-            lo.append((h.min() * 4) // 128)
-            hi.append(((h.max() + st.R) * 4 - 1) // 128)
+            if getattr(st, "scatter", 1) > 1:  # an example's rows lie all over the table: every distinct row's own interval
+                u = np.unique(h)
+                lo.extend((u * 4) // 128)
+                hi.extend(((u + st.R) * 4 - 1) // 128)
+            else:
+                lo.append((h.min() * 4) // 128)
+                hi.append(((h.max() + st.R) * 4 - 1) // 128)
         lr_sets.append(np.unique(fb.lr_buffer["hash"]))
         pos += m
     assert pos == len(st.hash)
