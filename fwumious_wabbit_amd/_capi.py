@@ -31,6 +31,11 @@ NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
 CANDIDATE_INFO = np.dtype([("code", "<i4"), ("is_delta", "u1"), ("record_ok", "u1"), ("by_host", "u1"), ("pad", "u1"), ("n_lr", "<u4"),
                            ("n_ffm", "<u4")])  # fwgpu_candidate_info
+_SUMS = [("n", "<u8"), ("n_unlabelled", "<u8"), ("n_bad", "<u8"), ("sum_importance", "<f8"), ("sum_loss", "<f8"), ("sum_loss_plain", "<f8"),
+         ("sum_pred", "<f8"), ("sum_label", "<f8")]
+METRIC_SUMS = np.dtype(_SUMS)  # fwgpu_metric_sums
+METRIC_WINDOW = np.dtype([("first_number", "<u8"), ("learned", METRIC_SUMS), ("held_out", METRIC_SUMS)])  # fwgpu_metric_window
+METRIC_TOTAL = np.dtype([("sums", METRIC_SUMS), ("hist", "<u8", (2, 256))])  # fwgpu_metric_total: hist[class][bin], class 1 = label == 1
 LR_ENTRY = np.dtype([("hash", "<u4"), ("value", "<f4"), ("combo_index", "<u4")])
 FFM_ENTRY = np.dtype([("hash", "<u4"), ("value", "<f4"), ("contra_field_index", "<u4")])
 
@@ -195,6 +200,10 @@ def lib():
         "fwgpu_trainer_examples_seen": [vp, P(u64)],
         "fwgpu_trainer_set_holdout": [vp, u64, i32],
         "fwgpu_trainer_predictions": [vp, vp, u64, P(u64)],
+        "fwgpu_batch_metrics": [vp, u32, u32, i32, vp, vp, vp],
+        "fwgpu_trainer_set_metrics": [vp, u64],
+        "fwgpu_trainer_metrics": [vp, vp, u64, P(u64), vp, vp],
+        "fwgpu_debug_metrics": [vp, vp, vp, vp, u64, u32, u64, u32, vp, u64, P(u64), vp, vp, vp],
         "fwgpu_set_launch": [vp, u32, u32],
         "fwgpu_set_max_in_flight": [vp, u32],
         "fwgpu_delta_start": [vp, vp, vp, vp, u64, f32, vp],

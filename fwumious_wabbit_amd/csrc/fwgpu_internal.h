@@ -330,6 +330,41 @@ hipError_t launch_delta_start(const float *t, const float *s0, float *d, float *
 hipError_t launch_delta_finish(float *t, float *s0, const float *d, const float *D, uint64_t n, hipStream_t stream);
 hipError_t launch_coherence_probe(unsigned *scratch, int use_sc1, unsigned iters, unsigned blocks, hipStream_t stream);
 
+// ---- progressive / hold-out loss (metrics.hip): one launch scores n predictions against their labels into a window table and two totals
+constexpr uint64_t kMetricsNoLabel = 255;  // parser.rs:28 NO_LABEL, as translate_record turns it into a float
+struct MetricsLaunch {
+    const float *pred = nullptr;           // [n]
+    const float *label = nullptr;          // [n] and importance [n] (entry batches, host arrays), or ...
+    const float *importance = nullptr;
+    const uint32_t *records = nullptr;     // ... raw records: word 1 of example i's record is its label, word 2 its importance's bits
+    const uint64_t *rec_off = nullptr;     // [n] word offsets
+    const uint8_t *learned = nullptr;      // [n] 0: held out; NULL: learned_all says it for every example
+    int32_t learned_all = 1;
+    uint32_t n = 0;
+    uint64_t first_number = 1;             // stream number of example 0 (from 1)
+    uint64_t window = 0;                   // examples per window; 0: no window table, totals only
+    fwgpu_metric_sums *rows = nullptr;     // [2 * n_windows] window w's learned side at 2 w, its held-out side at 2 w + 1
+    uint64_t n_windows = 0;                // windows the table holds: an example beyond it reaches the totals only
+    fwgpu_metric_sums *totals = nullptr;   // [2] learned, held out
+    unsigned long long *hist = nullptr;    // [2 * 512] their histograms (NULL: none)
+};
+hipError_t launch_metrics(const MetricsLaunch &a, hipStream_t stream);
+// The window table of one stream of examples, on the device.  score() sizes it for the launch's last window (growing geometrically: a new
+// allocation, the old rows copied on the stream, the stream waited for once before the old one is freed) and enqueues the kernel; no other
+// call of it allocates.  fetch() waits for the stream.
+struct MetricsTable {
+    uint64_t window = 0;
+    fwgpu_metric_sums *d_rows = nullptr;
+    uint64_t cap = 0, used = 0;            // windows allocated / windows a launch has reached
+    void *d_totals = nullptr;              // 2 sums, then 2 x 512 histogram counts
+    int score(MetricsLaunch a, hipStream_t stream);
+    int fetch(uint64_t first_window, uint64_t n_windows, fwgpu_metric_window *rows, fwgpu_metric_total *learned, fwgpu_metric_total *held_out,
+              hipStream_t stream);
+    void release();
+};
+// where a batch's labels live (entry arrays or records) and its predictions, examples first .. first + n - 1
+void metrics_from_batch(const fwgpu_batch *b, uint32_t first, uint32_t n, MetricsLaunch *a);
+
 }  // namespace fwgpu
 
 struct fwgpu_block_cache;
@@ -418,6 +453,7 @@ struct fwgpu_regressor {
     fwgpu_batch *one = nullptr;
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
+    void *metrics_scratch = nullptr;  // fwgpu_batch_metrics: one set of sums and histograms on the device (metrics.hip)
 };
 
 // device buffers of one synchronous micro-batch (regressor.cpp "split pipeline")

@@ -924,6 +924,7 @@ int fwgpu_free(fwgpu_regressor *r) {
     head_scratch_free(r);
     if (r->pred_x) (void)hipFree(r->pred_x);
     if (r->pred_yi) (void)hipFree(r->pred_yi);
+    if (r->metrics_scratch) (void)hipFree(r->metrics_scratch);
     (void)hipFree(r->d_lr);
     (void)hipFree(r->d_ffm_w);
     (void)hipFree(r->d_ffm_acc);

@@ -58,6 +58,8 @@ struct fwgpu_trainer {
     // device text route: the launch windows of the piece in slot c (views of the parser's buffers), and the batch that owns the translator's device arrays
     std::vector<std::unique_ptr<fwgpu_batch>> views[2];
     fwgpu_batch *text_tr = nullptr;
+    // progressive / hold-out loss (fwgpu_trainer_set_metrics; metrics.hip): window 0 = off, nothing below is touched
+    MetricsTable metrics;
 };
 
 static bool predict_mode(const fwgpu_trainer *tr) {  // for the NEXT example (number seen + 1)
@@ -72,6 +74,18 @@ static int retire(fwgpu_trainer *tr, int c) {
     if (tr->slot_predict[c]) tr->preds.insert(tr->preds.end(), tr->pred_host[c], tr->pred_host[c] + tr->slot_n[c]);
     tr->slot_predict[c] = false;
     return FWGPU_OK;
+}
+
+// With metrics on, the launch of `b` that is on the compute stream is followed by the metrics kernel there: the batch's predictions against the batch's own
+// labels, the launch's first example being number `first_number` of the stream.  Every route leaves a prediction per example, learned or not: the example
+// kernels store it before the update phase, the batched head predict writes the batch's, and the example-by-example walk copies its own into b->pred.
+static int score_launch(fwgpu_trainer *tr, const fwgpu_batch *b, uint64_t first_number, bool learned) {
+    if (!tr->metrics.window || !b->n) return FWGPU_OK;
+    MetricsLaunch a;
+    metrics_from_batch(b, 0, b->n, &a);
+    a.first_number = first_number;
+    a.learned_all = learned ? 1 : 0;
+    return tr->metrics.score(a, tr->stream);
 }
 
 // first half of a host-fed launch: the records staged for slot c go into its device buffer (copy stream -> compute stream)
@@ -144,6 +158,7 @@ static int flush(fwgpu_trainer *tr, bool predict = false) {
     fwgpu_batch *b = tr->dev[c];
     rc = fwgpu_learn_batch(r, b, FWGPU_MODE_HOGWILD, predict ? 0 : 1, tr->stream);
     if (rc) return rc;
+    if ((rc = score_launch(tr, b, tr->seen - n + 1, !predict))) return rc;  // (`seen` already counts the staged examples)
     if ((rc = close_slot(tr, c, predict ? b->pred : nullptr, n))) return rc;
     return open_slot(tr);
 }
@@ -200,6 +215,7 @@ static int launch_text_piece(fwgpu_trainer *tr, fwgpu_text_parser *tp, int c, co
         }
         int rc = fwgpu_learn_batch(r, b, FWGPU_MODE_HOGWILD, w < P.n_windows_learn ? 1 : 0, tr->stream);
         if (rc) return rc;
+        if ((rc = score_launch(tr, b, tr->seen + 1 + first, w < P.n_windows_learn))) return rc;  // (`seen` counts the piece once it is launched)
     }
     const uint32_t n_pred = P.n_take - P.n_learn;
     return close_slot(tr, c, n_pred ? P.d_pred + P.n_learn : nullptr, n_pred);
@@ -604,6 +620,22 @@ int fwgpu_trainer_set_holdout(fwgpu_trainer *tr, uint64_t holdout_after, int tes
     return FWGPU_OK;
 }
 
+int fwgpu_trainer_set_metrics(fwgpu_trainer *tr, uint64_t window) {
+    if (!tr) return fail(FWGPU_ERR_INVALID, "NULL trainer");
+    if (tr->seen) return fail(FWGPU_ERR_INVALID, "set the metrics window before digesting");
+    tr->metrics.window = window;
+    return FWGPU_OK;
+}
+
+int fwgpu_trainer_metrics(fwgpu_trainer *tr, fwgpu_metric_window *rows, uint64_t cap, uint64_t *n_rows, fwgpu_metric_total *learned,
+                          fwgpu_metric_total *held_out) {
+    if (!tr || !n_rows) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *n_rows = tr->metrics.used;
+    if (rows && cap < tr->metrics.used) return fail(FWGPU_ERR_RANGE, "buffer too small for the windows");
+    FWGPU_HIP(hipSetDevice(tr->r->device));
+    return tr->metrics.fetch(0, rows ? tr->metrics.used : 0, rows, learned, held_out, tr->stream);
+}
+
 int fwgpu_trainer_predictions(fwgpu_trainer *tr, float *out, uint64_t cap, uint64_t *n) {
     if (!tr || !n) return fail(FWGPU_ERR_INVALID, "NULL argument");
     *n = tr->preds.size();
@@ -634,6 +666,7 @@ int fwgpu_trainer_free(fwgpu_trainer *tr) {
     (void)hipSetDevice(tr->r->device);
     if (tr->stream) (void)hipStreamSynchronize(tr->stream);
     if (tr->text_tr) fwgpu_batch_free(tr->text_tr);
+    tr->metrics.release();
     for (int i = 0; i < 2; i++) {
         if (tr->dev[i]) fwgpu_batch_free(tr->dev[i]);
         if (tr->rec[i]) (void)hipHostFree(tr->rec[i]);

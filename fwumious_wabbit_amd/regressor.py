@@ -174,6 +174,16 @@ class Batch:
         check(capi.lib().fwgpu_batch_predictions(self.h, ptr(out), self.n, stream))
         return out
 
+    def metrics(self, first=0, n=None, learned=False, stream=None):
+        """log loss of the batch's current predictions against its own labels, scored on the device: (sums, hist) -- a capi.METRIC_SUMS record
+        and the [2, 256] prediction histogram (class 1 = label == 1) of examples first .. first + n - 1"""
+        if n is None:
+            n = self.n - first
+        sums = np.zeros(1, dtype=capi.METRIC_SUMS)
+        hist = np.zeros((2, 256), dtype=np.uint64)
+        check(capi.lib().fwgpu_batch_metrics(self.h, first, n, int(learned), ptr(sums), ptr(hist), stream))
+        return sums[0], hist
+
     def close(self):
         if self.h:
             capi.lib().fwgpu_batch_free(self.h)
@@ -628,6 +638,22 @@ class HogwildTrainer:
         check(capi.lib().fwgpu_trainer_predictions(self.h, ptr(out), out.size, C.byref(n)))
         return out
 
+    def set_metrics(self, window):
+        """progressive validation (main.rs:246, 260-268): every launch is scored on the device into windows of `window` stream numbers, learned and
+        held-out examples apart; 0 = off (the default).  Before the first example is digested."""
+        check(capi.lib().fwgpu_trainer_set_metrics(self.h, window))
+
+    def metrics(self):
+        """(rows, learned, held_out) after block_until_workers_finished: rows is a capi.METRIC_WINDOW array, one record per window scored so far;
+        the other two are capi.METRIC_TOTAL records, the running sums and prediction histograms of the learned / the held-out examples"""
+        n = C.c_uint64()
+        check(capi.lib().fwgpu_trainer_metrics(self.h, None, 0, C.byref(n), None, None))
+        rows = np.zeros(n.value, dtype=capi.METRIC_WINDOW)
+        totals = np.zeros(2, dtype=capi.METRIC_TOTAL)
+        check(capi.lib().fwgpu_trainer_metrics(self.h, ptr(rows), rows.size, C.byref(n), totals[0:1].ctypes.data_as(C.c_void_p),
+                                               totals[1:2].ctypes.data_as(C.c_void_p)))
+        return rows[: n.value], totals[0], totals[1]
+
     def digest_cache(self, cache, max_records=0) -> int:
         """the example loop over a RecordCache opened for reading (main.rs:213-270), in native code"""
         n = C.c_uint64()
@@ -690,6 +716,32 @@ class HogwildTrainer:
             self.close()
         except Exception:
             pass
+
+
+Trainer = HogwildTrainer
+
+
+def debug_metrics(pred, label, importance, learned, first_number, window, launch=0, stream=None):
+    """the metrics kernel alone on host arrays (fwgpu_debug_metrics) -> (rows, learned total, held-out total)"""
+    pred, label, importance = (np.ascontiguousarray(a, dtype=np.float32) for a in (pred, label, importance))
+    learned = np.ascontiguousarray(learned, dtype=np.uint8)
+    n = C.c_uint64()
+    rows = np.zeros((len(pred) + window - 1) // window + 1, dtype=capi.METRIC_WINDOW)
+    totals = np.zeros(2, dtype=capi.METRIC_TOTAL)
+    check(capi.lib().fwgpu_debug_metrics(ptr(pred), ptr(label), ptr(importance), ptr(learned), first_number, len(pred), window, launch, ptr(rows), rows.size,
+                                         C.byref(n), totals[0:1].ctypes.data_as(C.c_void_p), totals[1:2].ctypes.data_as(C.c_void_p), stream))
+    return rows[: n.value], totals[0], totals[1]
+
+
+def binned_auc(hist):
+    """AUC from a [2, 256] prediction histogram (fwgpu_metric_total.hist: class 1 = label == 1): the probability that a positive example falls into a
+    higher bin than a negative one, a pair in the same bin counting one half.  nan when a class is empty."""
+    h = np.asarray(hist, dtype=np.float64).reshape(2, -1)
+    neg, pos = h[0], h[1]
+    if neg.sum() == 0 or pos.sum() == 0:
+        return float("nan")
+    below = np.cumsum(neg) - neg  # negatives in lower bins
+    return float((pos * (below + 0.5 * neg)).sum() / (pos.sum() * neg.sum()))
 
 
 def synth_records(n_namespaces, mean_extra, zipf_s, ids_per_ns, p_weighted, seed, first_example, n):

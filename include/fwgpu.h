@@ -399,6 +399,44 @@ int fwgpu_trainer_examples_seen(const fwgpu_trainer *tr, uint64_t *n);
 int fwgpu_trainer_set_holdout(fwgpu_trainer *tr, uint64_t holdout_after, int testonly);
 int fwgpu_trainer_predictions(fwgpu_trainer *tr, float *out, uint64_t cap, uint64_t *n);
 
+/* ---------------------------------------------------------------- progressive and hold-out loss, scored on the device
+ * The reference's example loop has a prediction for every example, made BEFORE the example is learned (main.rs:246) and written out
+ * (main.rs:260-268); the loss of those predictions is benchmark/calc_loss.py's.  Here a kernel (csrc/metrics.hip) scores the
+ * predictions a launch left in its batch against the batch's own labels, on the device: no prediction and no label crosses to the host.
+ * Per example, in f64: p = clip((double)pred, 1e-15, 1 - 1e-15), loss = label == 1 ? -log(p) : -log(1 - p).  An example whose label is
+ * the parser's NO_LABEL (parser.rs:28: 0xff, 255.0f) counts in n_unlabelled; otherwise one whose prediction is not finite counts in
+ * n_bad; neither enters a sum or a histogram.  Examples are numbered from 1; window w of size W covers the numbers w * W + 1 .. (w + 1) * W,
+ * and every window has a learned and a held-out side.  Integer fields and histograms are exact; the f64 sums are accumulated with
+ * atomic adds, so their last bits depend on the order of arrival. */
+typedef struct fwgpu_metric_sums {
+    uint64_t n, n_unlabelled, n_bad;       /* scored / NO_LABEL / prediction not finite */
+    double sum_importance, sum_loss;       /* sum_loss: importance * loss */
+    double sum_loss_plain, sum_pred, sum_label;
+} fwgpu_metric_sums;
+typedef struct fwgpu_metric_window {
+    uint64_t first_number;                 /* the window's first stream number */
+    fwgpu_metric_sums learned, held_out;
+} fwgpu_metric_window;
+/* hist[c * 256 + b]: scored examples of class c (1: label == 1, 0: the rest) whose raw f32 prediction falls into bin
+ * b = min(255, (int)(pred * 256)) of 256 equal bins over [0, 1]: calibration and a binned AUC without a label on the host */
+typedef struct fwgpu_metric_total {
+    fwgpu_metric_sums sums;
+    uint64_t hist[512];
+} fwgpu_metric_total;
+/* fwgpu_batch_metrics <= benchmark/calc_loss.py on the predictions of main.rs:246: scores the current predictions of the batch's
+ *   examples first .. first + n - 1 (entry batches: the batch's label / importance arrays; record batches: the records' words 1 and 2,
+ *   feature_buffer.rs:187-189) on `stream`, waits for it and returns one set of sums and, if hist512 is not NULL, that histogram.
+ *   `learned` is not interpreted here.  FWGPU_ERR_RANGE: first + n beyond the batch.
+ * fwgpu_trainer_set_metrics <= the progressive validation of main.rs:246, 260-268: window > 0 turns scoring on, every launch of the
+ *   trainer (learn and predict-only, on every route) is followed by the metrics kernel on the trainer's stream; 0 (the default) is off.
+ *   FWGPU_ERR_INVALID once examples have been digested.
+ * fwgpu_trainer_metrics: after fwgpu_finish, the windows scored so far (rows == NULL: *n_rows only; cap < *n_rows: FWGPU_ERR_RANGE) and
+ *   the running totals of the learned and of the held-out examples (either may be NULL).  Metrics off: no rows, zero totals. */
+int fwgpu_batch_metrics(fwgpu_batch *b, uint32_t first, uint32_t n, int learned, fwgpu_metric_sums *out, uint64_t *hist512, void *stream);
+int fwgpu_trainer_set_metrics(fwgpu_trainer *tr, uint64_t window);
+int fwgpu_trainer_metrics(fwgpu_trainer *tr, fwgpu_metric_window *rows, uint64_t cap, uint64_t *n_rows, fwgpu_metric_total *learned,
+                          fwgpu_metric_total *held_out);
+
 /* ---------------------------------------------------------------- launch tuning (optional)
  * threads: workgroup size (multiple of 64, <=1024); workgroups_per_cu: persistent grid = CUs*this.
  * 0 keeps the default.  Does not change results in SEQUENTIAL mode. */
@@ -540,6 +578,14 @@ int fwgpu_debug_sparse_reduce(const void *keys, uint32_t n, int key_bits, const 
 int fwgpu_debug_sparse_apply(const uint32_t *all_key, const float *all_rows, const uint32_t *counts, uint32_t n_ranks, uint32_t stride, int key_bits,
                              uint32_t R, uint32_t k4, float *w, float *acc, int optimizer, float rate, float minus_power_t, const float *lut,
                              void *stream);
+/* The metrics kernel (metrics.hip) alone on host arrays, for tests against a float64 restatement (tests/metrics_ref.py): pred, label,
+ * importance [n] and learned [n] (0: held out) go to device buffers, the examples are numbered first_number .. first_number + n - 1
+ * (first_number >= 1) and scored in launches of at most `launch` examples (0: one launch) into a window table that starts empty and grows
+ * as a trainer's does.  Out: the windows from first_number's to the last example's (cap < *n_rows: FWGPU_ERR_RANGE; rows == NULL: the
+ * count only) and the two totals (either may be NULL).  window == 0 is FWGPU_ERR_INVALID. */
+int fwgpu_debug_metrics(const float *pred, const float *label, const float *importance, const uint8_t *learned, uint64_t first_number,
+                        uint32_t n, uint64_t window, uint32_t launch, fwgpu_metric_window *rows, uint64_t cap, uint64_t *n_rows,
+                        fwgpu_metric_total *learned_total, fwgpu_metric_total *held_out_total, void *stream);
 
 /* ---------------------------------------------------------------- feed path: namespace map, VW text parser, input cache
  * (SURVEY.md 8 f1/f3).  Host-side code; none of it needs a device.
