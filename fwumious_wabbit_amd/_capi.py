@@ -250,6 +250,11 @@ def lib():
         "fwgpu_model_load": [C.c_char_p, i32, i32, P(vp), P(vp), P(vp)],
         "fwgpu_model_load_packed": [C.c_char_p, i32, P(vp), P(vp), P(vp)],
         "fwgpu_ffm_storage": [vp, P(i32), P(u64)],
+        "fwgpu_quantize_ffm_table": [vp, vp, u64, P(u64)],
+        "fwgpu_model_save_inference": [C.c_char_p, vp, vp, vp, i32],
+        "fwgpu_pack_regressor": [vp, P(vp)],
+        "fwgpu_debug_quantize": [i32, vp, u64, vp, u64, P(i32)],
+        "fwgpu_debug_quantize_rates": [vp, vp],
         "fwgpu_set_wiring": [vp, i32],
         "fwgpu_model_convert_inference": [C.c_char_p, C.c_char_p, i32],
         "fwgpu_quantize_ffm_weights": [vp, u64, vp, u64],

@@ -330,6 +330,14 @@ hipError_t launch_delta_start(const float *t, const float *s0, float *d, float *
 hipError_t launch_delta_finish(float *t, float *s0, const float *d, const float *D, uint64_t n, hipStream_t stream);
 hipError_t launch_coherence_probe(unsigned *scratch, int use_sc1, unsigned iters, unsigned blocks, hipStream_t stream);
 
+// ---- the FFM weight quantiser on the device (quantize.hip; its header comment states the bit-exact contract with quantize_ffm)
+constexpr uint32_t kQuantGridCap = 2048;                  // workgroups of 256 lanes, four weights per lane: 2^21 weights per sweep of the grid
+constexpr size_t kQuantWsWords = 3 * (kQuantGridCap + 1); // statistics workspace: the result {min bits, max bits, not-finite flag}, then one triple per workgroup
+hipError_t launch_quant_stats(const float *w, uint64_t n, uint32_t *ws, hipStream_t stream);
+hipError_t launch_quant_buckets(const float *w, uint64_t n, float increment, float mn, uint16_t *q, hipStream_t stream);
+hipError_t launch_lr_weights(const float *pairs, uint64_t n_entries, float *w, hipStream_t stream);                // {w, acc} pairs -> w
+hipError_t launch_lr_weights_pairs(const float *pairs, uint64_t n_entries, float *dst_pairs, hipStream_t stream);  // {w, acc} pairs -> {w, 0} pairs
+
 // ---- progressive / hold-out loss (metrics.hip): one launch scores n predictions against their labels into a window table and two totals
 constexpr uint64_t kMetricsNoLabel = 255;  // parser.rs:28 NO_LABEL, as translate_record turns it into a float
 struct MetricsLaunch {
@@ -640,6 +648,20 @@ void lut_init(float *lut, float learning_rate, float power_t, float init_acc);
 KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int update);
 int refuse_packed(const fwgpu_regressor *r, const char *what);  // FWGPU_ERR_INVALID on a packed regressor, FWGPU_OK otherwise
 int create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out);
+// ---- quantising a live regressor's FFM weights (model_file.cpp: the host quantiser; regressor.cpp: the device route and its callers)
+// quantization.rs:42-80 on the host: out = 8-byte header {increment, min} + n f16 bucket numbers
+void quantize_ffm(const float *w, uint64_t n, std::vector<uint8_t> &out);
+// the header of that block from a table's minimum and maximum (the one copy of these statements: quantize_ffm and the device route both call it)
+void quantize_header(float mn, float mx, float *increment, float *min_rounded);
+bool quantize_host_forced();  // FWGPU_QUANTIZE_HOST=1: every caller below takes the host route (A/B runs)
+// d_w[n] (device) -> d_q[n] bucket numbers (device) and the header.  *done = false: the contract sends this table to the host route (a weight that is not
+// finite, an increment that is 0 or not finite, or FWGPU_QUANTIZE_HOST) and d_q was not written.  The device is idle when it returns.
+int quantize_on_device(int device, const float *d_w, uint64_t n, uint16_t *d_q, float *increment, float *mn, bool *done);
+// the regressor's FFM weights as the quantised block (8 + 2 ffm_len bytes), device route where the contract allows; waits for the regressor's launches
+int ffm_quantized_block(fwgpu_regressor *r, std::vector<uint8_t> &out, bool *on_device = nullptr);
+// the regressor's LR weights without their accumulators [lr_len], compacted on the device; and its dense layers' weights in block order
+int lr_weights_read(fwgpu_regressor *r, float *host_out);
+int nn_weights_read(fwgpu_regressor *r, std::vector<float> &out);
 // the fused learn / predict launch of `b` with every row and LR entry reached in its owner's tables (generic kernel); d_shards: device copy
 int run_batch_peer(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, const PeerShards *d_shards, hipStream_t stream,
                    const PushRings *d_push = nullptr, uint32_t stream_consumers = 0, uint32_t device_share = 1, uint32_t stream_max_consumer_waves = 0, uint32_t n_ranks = 0);

@@ -347,16 +347,25 @@ float f16_to_f32(uint16_t h) {
     return f;
 }
 
+}  // namespace
+
+// quantization.rs:52-58: the block's header from the table's extremes (the device route forms it from its own reduced pair: quantize.hip)
+void fwgpu::quantize_header(float mn, float mx, float *increment, float *min_rounded) {
+    mn = std::round(mn * 10000.0f) / 10000.0f;  // MIN_PREC / MAX_PREC
+    mx = std::round(mx * 10000.0f) / 10000.0f;
+    *increment = (mx - mn) / 65025.0f;          // NUM_BUCKETS
+    *min_rounded = mn;
+}
+
 // quantization.rs:18-41 emit_weight_statistics + 42-80 quantize_ffm_weights: 8-byte header {increment, min} + f16 buckets
-void quantize_ffm(const float *w, uint64_t n, std::vector<uint8_t> &out) {
+void fwgpu::quantize_ffm(const float *w, uint64_t n, std::vector<uint8_t> &out) {
     float mn = w[0], mx = w[0];
     for (uint64_t i = 0; i < n; i++) {
         mx = std::fmax(mx, w[i]);
         mn = std::fmin(mn, w[i]);
     }
-    mn = std::round(mn * 10000.0f) / 10000.0f;  // MIN_PREC / MAX_PREC
-    mx = std::round(mx * 10000.0f) / 10000.0f;
-    const float inc = (mx - mn) / 65025.0f;     // NUM_BUCKETS
+    float inc;
+    quantize_header(mn, mx, &inc, &mn);
     out.resize(8 + 2 * n);
     std::memcpy(out.data(), &inc, 4);
     std::memcpy(out.data() + 4, &mn, 4);
@@ -366,6 +375,8 @@ void quantize_ffm(const float *w, uint64_t n, std::vector<uint8_t> &out) {
         out[9 + 2 * i] = (uint8_t)(h >> 8);
     }
 }
+
+namespace {
 void dequantize_ffm(const uint8_t *src, uint64_t n, float *w) {  // quantization.rs:82-98
     float inc, mn;
     std::memcpy(&inc, src, 4);
@@ -619,6 +630,8 @@ int fwgpu_model_save(const char *path, const fwgpu_vwmap *vw, const fwgpu_model_
         uint64_t written = 0;
         rc = fwgpu_write_weights(r, blob.data(), blob.size(), &written);
         if (rc) return rc;
+        std::vector<uint8_t> q;  // the FFM block, made from the table on the device where quantize.hip's contract allows: the bytes of quantize_ffm on the blob
+        if (quantize_weights && s.ffm_len && (rc = ffm_quantized_block(r, q))) return rc;
         File out;
         out.f = std::fopen(path, "wb");
         if (!out.f) return fail(FWGPU_ERR_IO, std::string("Cannot open ") + path + " to save regressor to");
@@ -629,8 +642,6 @@ int fwgpu_model_save(const char *path, const fwgpu_vwmap *vw, const fwgpu_model_
             const bool sgd = mi->optimizer == FWGPU_OPT_SGD;
             const uint64_t lr_bytes = s.lr_len * (sgd ? 4 : 8);
             out.put(blob.data(), 8 + lr_bytes);
-            std::vector<uint8_t> q;
-            quantize_ffm(reinterpret_cast<const float *>(blob.data() + 8 + lr_bytes), s.ffm_len, q);
             out.put(q.data(), q.size());
             const uint64_t rest = 8 + lr_bytes + s.ffm_len * 4;
             out.put(blob.data() + rest, written - rest);
@@ -638,6 +649,56 @@ int fwgpu_model_save(const char *path, const fwgpu_vwmap *vw, const fwgpu_model_
         if (std::fclose(out.f) != 0) {
             out.f = nullptr;
             return fail(FWGPU_ERR_IO, "model_save: close failed");
+        }
+        out.f = nullptr;
+    } catch (const std::exception &e) {
+        return fail(FWGPU_ERR_IO, e.what());
+    }
+    return FWGPU_OK;
+}
+
+// main.rs:136-148 from a live training regressor: the file fwgpu_model_save followed by fwgpu_model_convert_inference writes, without the
+// training file and without the accumulator tables leaving the device (include/fwgpu.h)
+int fwgpu_model_save_inference(const char *path, const fwgpu_vwmap *vw, const fwgpu_model_instance *mi, fwgpu_regressor *r,
+                               int quantize_weights) {
+    if (!path || !vw || !mi || !r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    int rc = refuse_packed(r, "model_save_inference");
+    if (rc) return rc;
+    BlobShape s;
+    rc = shape_from_mi(mi, &s);
+    if (rc) return rc;
+    uint64_t need = 0;
+    rc = fwgpu_serialized_len(r, &need);
+    if (rc) return rc;
+    if (mi->optimizer != r->cfg.optimizer || need != 8 + blob_body_bytes(r->cfg.optimizer, false, s))
+        return fail(FWGPU_ERR_INVALID, "model_save_inference: the regressor was not built from this ModelInstance");
+    try {
+        fwgpu_model_instance inf = *mi;
+        fwgpu_mi_set_inference(&inf, quantize_weights);
+        std::vector<float> lr(s.lr_len), nn;
+        rc = lr_weights_read(r, lr.data());  // compacted on the device: block_lr's weights without their accumulators
+        if (rc) return rc;
+        std::vector<uint8_t> ffm;
+        if (s.ffm_len && quantize_weights) {
+            rc = ffm_quantized_block(r, ffm);
+        } else if (s.ffm_len) {
+            ffm.resize(s.ffm_len * 4);
+            rc = fwgpu_table_read(r, FWGPU_TABLE_FFM_W, 0, s.ffm_len, reinterpret_cast<float *>(ffm.data()));
+        }
+        if (rc) return rc;
+        rc = nn_weights_read(r, nn);  // (small: through the host as they are)
+        if (rc) return rc;
+        File out;
+        out.f = std::fopen(path, "wb");
+        if (!out.f) return fail(FWGPU_ERR_IO, std::string("Cannot open ") + path + " to save regressor to");
+        write_header(out, vw, &inf);
+        out.put_u64(s.elems());
+        out.put(lr.data(), lr.size() * 4);
+        out.put(ffm.data(), ffm.size());
+        out.put(nn.data(), nn.size() * 4);
+        if (std::fclose(out.f) != 0) {
+            out.f = nullptr;
+            return fail(FWGPU_ERR_IO, "model_save_inference: close failed");
         }
         out.f = nullptr;
     } catch (const std::exception &e) {

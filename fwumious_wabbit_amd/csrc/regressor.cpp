@@ -2,6 +2,7 @@
 // single-example learn/predict (regressor.rs:356-395), micro-batches, and weight (de)serialisation
 // (regressor.rs:426-469).  There is no CPU compute path: every learn/predict runs the HIP kernel.
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -815,8 +816,8 @@ static int place_ffm_acc(fwgpu_regressor *r, size_t fbytes) {
     return FWGPU_OK;
 }
 
-static int create_impl(const fwgpu_config *cfg, const uint8_t *packed_blob, fwgpu_regressor **out);
-int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) { return create_impl(cfg, nullptr, out); }
+static int create_impl(const fwgpu_config *cfg, bool packed, const uint8_t *packed_blob, fwgpu_regressor **out);
+int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) { return create_impl(cfg, false, nullptr, out); }
 
 }  // extern "C"
 
@@ -830,7 +831,7 @@ int fwgpu::create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8
         return fail(FWGPU_ERR_INVALID, "packed regressor: ffm_k must be a multiple of 4 and a row (ffm_k x fields) at most 256 weights, or at most 512 with ffm_k dividing 256; got ffm_k = " +
                                            std::to_string(cfg->ffm_k) + ", fields = " + std::to_string(cfg->ffm_num_fields));
     fwgpu_regressor *r = nullptr;
-    int rc = create_impl(cfg, blob, &r);
+    int rc = create_impl(cfg, true, blob, &r);
     if (rc) return rc;
     std::vector<float> tmp(r->lr_len * 2, 0.0f);
     for (uint64_t i = 0; i < r->lr_len; i++) tmp[2 * i] = lr_w[i];
@@ -844,7 +845,8 @@ int fwgpu::create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8
 
 extern "C" {
 
-static int create_impl(const fwgpu_config *cfg, const uint8_t *packed_blob, fwgpu_regressor **out) {
+// packed: the FFM weights are a table of bucket numbers, filled from packed_blob or, without one, by the caller (fwgpu_pack_regressor)
+static int create_impl(const fwgpu_config *cfg, bool packed, const uint8_t *packed_blob, fwgpu_regressor **out) {
     if (!cfg || !out) return fail(FWGPU_ERR_INVALID, "fwgpu_create: NULL argument");
     *out = nullptr;
     if (cfg->optimizer != FWGPU_OPT_SGD && cfg->optimizer != FWGPU_OPT_ADAGRAD_FLEX &&
@@ -881,14 +883,16 @@ static int create_impl(const fwgpu_config *cfg, const uint8_t *packed_blob, fwgp
     // (where the LR table lands relative to the FFM tables was measured not to matter: 3.55 ms per launch either way)
     FWGPU_HIP(hipMalloc((void **)&r->d_lr, r->lr_len * 2 * sizeof(float)));
     FWGPU_HIP(hipMemset(r->d_lr, 0, r->lr_len * 2 * sizeof(float)));
-    if (r->ffm_len && packed_blob) {
+    if (r->ffm_len && packed) {
         // (+128 bytes of slack: the 8-byte vector of a lane beyond the last row's end stays in the allocation even without the descriptor's bound)
         r->ffm_q_bytes = r->ffm_len * 2 + 128;
         FWGPU_HIP(hipMalloc((void **)&r->d_ffm_q, r->ffm_q_bytes));
-        memcpy(&r->q_increment, packed_blob, 4);
-        memcpy(&r->q_min, packed_blob + 4, 4);
         FWGPU_HIP(hipMemset(reinterpret_cast<unsigned char *>(r->d_ffm_q) + r->ffm_len * 2, 0, 128));
-        FWGPU_HIP(hipMemcpy(r->d_ffm_q, packed_blob + 8, r->ffm_len * 2, hipMemcpyHostToDevice));
+        if (packed_blob) {
+            memcpy(&r->q_increment, packed_blob, 4);
+            memcpy(&r->q_min, packed_blob + 4, 4);
+            FWGPU_HIP(hipMemcpy(r->d_ffm_q, packed_blob + 8, r->ffm_len * 2, hipMemcpyHostToDevice));
+        }
     } else if (r->ffm_len) {
         // +64 floats of slack so that a 16 B vector at the very end of the spill-over tail stays in the allocation
         const size_t fbytes = (r->ffm_len + 64) * sizeof(float);
@@ -2078,6 +2082,246 @@ int fwgpu_read_weights(fwgpu_regressor *r, const uint8_t *buf, uint64_t len) {
             o += len * 4;
         }
     }
+    return FWGPU_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ quantising on the device (quantize.hip): inference save, pack, refresh
+namespace fwgpu {
+
+bool quantize_host_forced() {
+    const char *env = getenv("FWGPU_QUANTIZE_HOST");  // A/B runs (scripts/bench_publish.py); read at every call: publishing is no hot path
+    return env && atoi(env) != 0;
+}
+
+int quantize_on_device(int device, const float *d_w, uint64_t n, uint16_t *d_q, float *increment, float *mn, bool *done) {
+    *done = false;
+    if (quantize_host_forced() || !n) return FWGPU_OK;
+    FWGPU_HIP(hipSetDevice(device));
+    uint32_t *ws = nullptr;
+    FWGPU_HIP(hipMalloc((void **)&ws, kQuantWsWords * sizeof(uint32_t)));
+    uint32_t st[3] = {0, 0, 1};
+    hipError_t e = launch_quant_stats(d_w, n, ws, 0);
+    if (e == hipSuccess) e = hipMemcpy(st, ws, sizeof st, hipMemcpyDeviceToHost);
+    (void)hipFree(ws);
+    if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("quantize (statistics): ") + hipGetErrorString(e));
+    float lo, hi;
+    memcpy(&lo, &st[0], 4);
+    memcpy(&hi, &st[1], 4);
+    quantize_header(lo, hi, increment, mn);
+    if (st[2] || *increment == 0.0f || !isfinite(*increment)) return FWGPU_OK;  // the host route's cases (quantize.hip)
+    FWGPU_HIP(launch_quant_buckets(d_w, n, *increment, *mn, d_q, 0));
+    FWGPU_HIP(hipDeviceSynchronize());
+    *done = true;
+    return FWGPU_OK;
+}
+
+// the host route: the table crosses to the host and quantize_ffm runs there
+static int ffm_block_on_host(fwgpu_regressor *r, std::vector<uint8_t> &out) {
+    std::vector<float> w(r->ffm_len);
+    int rc = fwgpu_table_read(r, FWGPU_TABLE_FFM_W, 0, r->ffm_len, w.data());
+    if (rc) return rc;
+    quantize_ffm(w.data(), r->ffm_len, out);
+    return FWGPU_OK;
+}
+
+int ffm_quantized_block(fwgpu_regressor *r, std::vector<uint8_t> &out, bool *on_device) {
+    if (on_device) *on_device = false;
+    int rc = refuse_packed(r, "quantize_ffm_table");
+    if (rc) return rc;
+    if (!r->ffm_len) return fail(FWGPU_ERR_INVALID, "quantize_ffm_table: the model has no FFM block");
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    if (quantize_host_forced()) return ffm_block_on_host(r, out);
+    uint16_t *d_q = nullptr;
+    if (hipMalloc((void **)&d_q, r->ffm_len * 2) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FWGPU_ERR_OOM, "quantize_ffm_table: no device memory for the bucket table");
+    }
+    float inc = 0, mn = 0;
+    bool done = false;
+    rc = quantize_on_device(r->device, r->d_ffm_w, r->ffm_len, d_q, &inc, &mn, &done);
+    if (!rc && done) {
+        out.resize(8 + 2 * r->ffm_len);
+        memcpy(out.data(), &inc, 4);
+        memcpy(out.data() + 4, &mn, 4);
+        if (hipMemcpy(out.data() + 8, d_q, r->ffm_len * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FWGPU_ERR_DEVICE, "quantize_ffm_table: bucket download failed");
+    }
+    (void)hipFree(d_q);
+    if (rc) return rc;
+    if (!done) return ffm_block_on_host(r, out);
+    if (on_device) *on_device = true;
+    return FWGPU_OK;
+}
+
+int lr_weights_read(fwgpu_regressor *r, float *host_out) {
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    if (quantize_host_forced()) {  // the pairs cross, the host drops the accumulators (what fwgpu_write_weights + to_weights_only do)
+        std::vector<float> tmp(r->lr_len * 2);
+        FWGPU_HIP(hipMemcpy(tmp.data(), r->d_lr, r->lr_len * 8, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < r->lr_len; i++) host_out[i] = tmp[2 * i];
+        return FWGPU_OK;
+    }
+    float *d = nullptr;
+    if (hipMalloc((void **)&d, r->lr_len * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FWGPU_ERR_OOM, "no device memory for the compacted LR weights");
+    }
+    hipError_t e = launch_lr_weights(r->d_lr, r->lr_len, d, 0);
+    if (e == hipSuccess) e = hipMemcpy(host_out, d, r->lr_len * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("LR weights: ") + hipGetErrorString(e));
+    return FWGPU_OK;
+}
+
+int nn_weights_read(fwgpu_regressor *r, std::vector<float> &out) {
+    out.clear();
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    for (uint32_t l = 0; r->nn.n_layers && l <= r->nn.n_layers; l++) {  // block order, as fwgpu_write_weights walks them
+        const size_t len = ((size_t)r->nn.in[l] + 1) * r->nn.out[l], at = out.size();
+        out.resize(at + len);
+        FWGPU_HIP(hipMemcpy(out.data() + at, r->d_nn_w + r->nn.off[l], len * 4, hipMemcpyDeviceToHost));
+    }
+    return FWGPU_OK;
+}
+
+}  // namespace fwgpu
+
+extern "C" {
+
+int fwgpu_quantize_ffm_table(fwgpu_regressor *r, uint8_t *out, uint64_t cap, uint64_t *written) {
+    if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    int rc = refuse_packed(r, "quantize_ffm_table");
+    if (rc) return rc;
+    if (!r->ffm_len) return fail(FWGPU_ERR_INVALID, "quantize_ffm_table: the model has no FFM block");
+    if (cap < 8 + 2 * r->ffm_len) return fail(FWGPU_ERR_RANGE, "quantize_ffm_table: buffer too small");
+    std::vector<uint8_t> q;
+    rc = ffm_quantized_block(r, q);
+    if (rc) return rc;
+    memcpy(out, q.data(), q.size());
+    if (written) *written = q.size();
+    return FWGPU_OK;
+}
+
+int fwgpu_pack_regressor(fwgpu_regressor *src, fwgpu_regressor **out) {
+    if (!src || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    int rc = refuse_packed(src, "pack_regressor (the source)");
+    if (rc) return rc;
+    // the refusals of fwgpu_model_load_packed, in its words
+    if (src->nn.n_layers) return fail(FWGPU_ERR_INVALID, "model_load_packed: models with a deep head are not served from packed weights");
+    if (!src->ffm_len) return fail(FWGPU_ERR_INVALID, "model_load_packed: the model has no FFM block, there is nothing to pack");
+    if (!packed_shape_ok(src->cfg.ffm_k, src->cfg.ffm_num_fields))
+        return fail(FWGPU_ERR_INVALID, "packed regressor: ffm_k must be a multiple of 4 and a row (ffm_k x fields) at most 256 weights, or at most 512 with ffm_k dividing 256; got ffm_k = " +
+                                           std::to_string(src->cfg.ffm_k) + ", fields = " + std::to_string(src->cfg.ffm_num_fields));
+    fwgpu_regressor *dst = *out;
+    if (dst) {
+        const fwgpu_config &a = src->cfg, &b = dst->cfg;
+        if (!dst->packed() || dst->device != src->device || dst->lr_len != src->lr_len || dst->ffm_len != src->ffm_len || a.ffm_k != b.ffm_k ||
+            a.ffm_num_fields != b.ffm_num_fields || a.bit_precision != b.bit_precision || a.ffm_bit_precision != b.ffm_bit_precision ||
+            a.num_combos != b.num_combos)
+            return fail(FWGPU_ERR_INVALID, "pack_regressor: the target is not a packed regressor of the source's geometry on the source's device");
+    }
+    FWGPU_HIP(hipSetDevice(src->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    std::vector<uint8_t> host_block;
+    const bool own = dst == nullptr;
+    if (own) {
+        fwgpu_config cfg = src->cfg;
+        cfg.optimizer = FWGPU_OPT_SGD;           // persistence.rs:164 (immutable)
+        cfg.wiring = FWGPU_WIRING_REGRESSOR;     // (a model file carries no wiring)
+        rc = create_impl(&cfg, true, nullptr, &dst);
+        if (rc) return rc;
+    }
+    float inc = 0, mn = 0;
+    bool done = false;
+    // table to table on the device; a table the contract sends to the host route (quantize.hip) leaves the target's buckets unwritten until the host's block is there
+    rc = quantize_on_device(src->device, src->d_ffm_w, src->ffm_len, dst->d_ffm_q, &inc, &mn, &done);
+    if (!rc && !done) rc = ffm_block_on_host(src, host_block);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        if (!done) {
+            memcpy(&inc, host_block.data(), 4);
+            memcpy(&mn, host_block.data() + 4, 4);
+            e = hipMemcpy(dst->d_ffm_q, host_block.data() + 8, src->ffm_len * 2, hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) e = launch_lr_weights_pairs(src->d_lr, src->lr_len, dst->d_lr, 0);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail(FWGPU_ERR_DEVICE, std::string("pack_regressor: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        if (own) fwgpu_free(dst);
+        return rc;
+    }
+    dst->q_increment = inc;
+    dst->q_min = mn;
+    *out = dst;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_quantize(int device, const float *weights, uint64_t n, uint8_t *out, uint64_t cap, int *on_device) {
+    if (!weights || !out || n == 0) return fail(FWGPU_ERR_INVALID, "NULL / empty argument");
+    if (cap < 8 + 2 * n) return fail(FWGPU_ERR_RANGE, "buffer too small");
+    if (on_device) *on_device = 0;
+    FWGPU_HIP(hipSetDevice(device));
+    float *d_w = nullptr;
+    uint16_t *d_q = nullptr;
+    hipError_t e = hipMalloc((void **)&d_w, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_q, n * 2);
+    if (e == hipSuccess) e = hipMemcpy(d_w, weights, n * 4, hipMemcpyHostToDevice);
+    float inc = 0, mn = 0;
+    bool done = false;
+    int rc = e == hipSuccess ? quantize_on_device(device, d_w, n, d_q, &inc, &mn, &done) : fail(FWGPU_ERR_DEVICE, std::string("debug_quantize: ") + hipGetErrorString(e));
+    if (!rc && done) {
+        memcpy(out, &inc, 4);
+        memcpy(out + 4, &mn, 4);
+        if (hipMemcpy(out + 8, d_q, n * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FWGPU_ERR_DEVICE, "debug_quantize: bucket download failed");
+    }
+    (void)hipFree(d_w);
+    (void)hipFree(d_q);
+    if (rc) return rc;
+    if (!done) return fwgpu_quantize_ffm_weights(weights, n, out, cap);  // the host route, as every caller of quantize_on_device takes it
+    if (on_device) *on_device = 1;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_quantize_rates(fwgpu_regressor *r, float *ms3) {
+    if (!r || !ms3) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    int rc = refuse_packed(r, "debug_quantize_rates");
+    if (rc) return rc;
+    if (!r->ffm_len) return fail(FWGPU_ERR_INVALID, "debug_quantize_rates: the model has no FFM block");
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    const uint64_t n = r->ffm_len;
+    void *scratch = nullptr;  // the copy's destination; its first half takes the buckets
+    uint32_t *ws = nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipMalloc(&scratch, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws, kQuantWsWords * sizeof(uint32_t));
+    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+    float w[2] = {0, 0}, inc = 0, mn = 0;
+    if (e == hipSuccess) e = hipEventRecord(ev[0], 0);
+    if (e == hipSuccess) e = launch_quant_stats(r->d_ffm_w, n, ws, 0);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
+    if (e == hipSuccess) e = hipMemcpy(w, ws, sizeof w, hipMemcpyDeviceToHost);
+    quantize_header(w[0], w[1], &inc, &mn);
+    if (e == hipSuccess && (inc == 0.0f || !isfinite(inc))) inc = 1.0f;  // (a table of the host route: the kernel's time does not depend on the values)
+    if (e == hipSuccess) e = hipEventRecord(ev[2], 0);  // (the device was idle while the host formed the header)
+    if (e == hipSuccess) e = launch_quant_buckets(r->d_ffm_w, n, inc, mn, static_cast<uint16_t *>(scratch), 0);
+    if (e == hipSuccess) e = hipEventRecord(ev[3], 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(scratch, r->d_ffm_w, n * 4, hipMemcpyDeviceToDevice, 0);
+    if (e == hipSuccess) e = hipEventRecord(ev[4], 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[4]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms3[0], ev[0], ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms3[1], ev[2], ev[3]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms3[2], ev[3], ev[4]);
+    for (int i = 0; i < 5; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    (void)hipFree(scratch);
+    (void)hipFree(ws);
+    if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("debug_quantize_rates: ") + hipGetErrorString(e));
     return FWGPU_OK;
 }
 

@@ -107,6 +107,18 @@ def save_regressor_to_filename(filename: str, mi: ModelInstance, vwmap: VwNamesp
     h.close()
 
 
+def save_inference_regressor(filename: str, mi: ModelInstance, vwmap: VwNamespaceMap, re: Regressor,
+                             quantize_weights: bool = False, extra=None):
+    """main.rs:136-148 straight from a live training regressor: the file save_regressor_to_filename followed by
+    convert_inference_regressor(quantize_weights) writes, with the weights compacted / quantised on the device and the
+    accumulators left there (fwgpu_model_save_inference)"""
+    h = ModelInstanceHandle.from_model_instance(mi, extra)
+    try:
+        capi.check(capi.lib().fwgpu_model_save_inference(filename.encode(), vwmap.h, h.h, re.h, int(quantize_weights)))
+    finally:
+        h.close()
+
+
 def load_regressor_without_weights(filename: str):
     """persistence.rs:91-125 (header only) -> (ModelInstanceHandle, VwNamespaceMap)"""
     L = capi.lib()

@@ -12,7 +12,7 @@ the reference's own tests:
 All compute happens in libfwgpu.so on the GPU; nothing here falls back to the CPU.
 """
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -535,6 +535,24 @@ class Regressor:
         check(self.L.fwgpu_ffm_storage(self.h, C.byref(st), C.byref(nb)))
         return st.value, nb.value
 
+    def quantize_ffm_table(self) -> bytes:
+        """the FFM weights as the inference file's quantised block (8-byte header {increment, min} + one f16 bucket per weight), made on the
+        device: the bytes of persistence.quantize_ffm_weights(table_read(TABLE_FFM_W)) -- fwgpu_quantize_ffm_table"""
+        out = np.zeros(8 + 2 * self.table_len(capi.TABLE_FFM_W), dtype=np.uint8)
+        w = C.c_uint64(0)
+        check(self.L.fwgpu_quantize_ffm_table(self.h, ptr(out), out.size, C.byref(w)))
+        return out[: w.value].tobytes()
+
+    def pack(self, into=None):
+        """the packed (f16 buckets, predict-only) regressor persistence.new_regressor_from_filename(file saved from this one, immutable=True,
+        packed=True) would give, made table to table on the device; into: a packed Regressor of the same geometry, refreshed in place (no
+        predict launch of it may be in flight on another stream) -- fwgpu_pack_regressor"""
+        h = C.c_void_p(into.h.value) if into is not None else C.c_void_p()
+        check(self.L.fwgpu_pack_regressor(self.h, C.byref(h)))
+        if into is not None:
+            return into
+        return Regressor.from_handle(replace(self.mi, optimizer=Optimizer.SGD, wiring=capi.WIRING_REGRESSOR), h)
+
     def table_len(self, which):
         n = C.c_uint64(0)
         check(self.L.fwgpu_table_len(self.h, which, C.byref(n)))
@@ -731,6 +749,16 @@ def debug_metrics(pred, label, importance, learned, first_number, window, launch
     check(capi.lib().fwgpu_debug_metrics(ptr(pred), ptr(label), ptr(importance), ptr(learned), first_number, len(pred), window, launch, ptr(rows), rows.size,
                                          C.byref(n), totals[0:1].ctypes.data_as(C.c_void_p), totals[1:2].ctypes.data_as(C.c_void_p), stream))
     return rows[: n.value], totals[0], totals[1]
+
+
+def debug_quantize(weights, device=0):
+    """the quantiser's statistics and bucket kernels alone on a host array of any length (fwgpu_debug_quantize) -> (the 8 + 2 n bytes,
+    True when the device made them / False when the contract sent the array to the host quantiser)"""
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    out = np.zeros(8 + 2 * w.size, dtype=np.uint8)
+    on_device = C.c_int(0)
+    check(capi.lib().fwgpu_debug_quantize(device, ptr(w), w.size, ptr(out), out.size, C.byref(on_device)))
+    return out.tobytes(), bool(on_device.value)
 
 
 def binned_auc(hist):

@@ -787,6 +787,39 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw, fwgp
 /* How the FFM weight table lives on the device, and the bytes it occupies there */
 enum { FWGPU_FFM_F32 = 0, FWGPU_FFM_F16_BUCKETS = 1 };
 int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes);
+/* ---- quantising on the device: train -> publish -> serve without the training blob crossing to the host
+ * The reference's quantiser (quantization.rs:18-80) as HIP kernels (csrc/quantize.hip): a statistics pass (min, max, "a weight is not finite")
+ * over exactly the table's weights, the header {increment, min} formed on the host from the two reduced floats by the host quantiser's own
+ * statements, and a bucket pass f16(roundf((w - min) / increment)).
+ * CONTRACT: the bytes are those of fwgpu_quantize_ffm_weights on the same weights.  HOST ROUTE: when a weight is NaN or infinite, or the
+ * header's increment is 0 or not finite (a constant table, a maximum that rounds onto the minimum), the device route is not used and the
+ * call quantises on the host as before (fwgpu_table_read + the host quantiser): those results are the host's by construction.
+ * OUTSIDE THE CONTRACT: a table whose extreme value is a zero present with both signs (fmin(+0, -0) is unspecified on the host): the sign
+ * of the header's min may differ.  FWGPU_QUANTIZE_HOST=1 in the environment forces the host route everywhere (A/B runs).
+ * Every call below first waits for the regressor's outstanding launches, as fwgpu_write_weights does, and leaves the source regressor's
+ * tables and its ability to train untouched. */
+/* The regressor's FFM weights as the quantised block: 8-byte header, then one f16 bucket per weight (8 + 2 n bytes, n = fwgpu_table_len of
+ * FWGPU_TABLE_FFM_W).  Only the buckets cross to the host.  FWGPU_ERR_INVALID for packed regressors and models without an FFM block. */
+int fwgpu_quantize_ffm_table(fwgpu_regressor *r, uint8_t *out, uint64_t cap, uint64_t *written);
+/* From a live training regressor, the file that fwgpu_model_save(training file) followed by fwgpu_model_convert_inference(...,
+ * quantize_weights) writes (main.rs:136-148), byte for byte: the header is that of a copy of `mi` after fwgpu_mi_set_inference; LR weights
+ * only (compacted on the device), FFM weights as f32 or as buckets, dense layers' weights only (small: through the host).  The
+ * accumulator tables never leave the device.  All three optimizers and models with a deep head are accepted. */
+int fwgpu_model_save_inference(const char *path, const fwgpu_vwmap *vw, const fwgpu_model_instance *mi, fwgpu_regressor *r,
+                               int quantize_weights);
+/* *out == NULL: creates, on src's device, the packed regressor fwgpu_model_load_packed would create from a file saved from src at this
+ * moment -- table to table on the device, no host copy of either -- with fwgpu_model_load_packed's refusals and messages (deep head, no FFM
+ * block, ffm_k % 4, row size).  *out != NULL: refreshes that packed regressor in place: buckets, the two header words the predict kernel
+ * takes as launch constants, and the LR weights.  It must be a packed regressor (made here or by fwgpu_model_load_packed) of src's
+ * geometry on src's device; anything else is FWGPU_ERR_INVALID and *out stays usable.  A packed src is refused.  The call waits for the
+ * device; the caller must not have predict launches of *out in flight on other streams while it runs. */
+int fwgpu_pack_regressor(fwgpu_regressor *src, fwgpu_regressor **out);
+/* debug: the statistics and bucket kernels on a host array of any length (uploaded, quantised, 8 + 2 n bytes returned); *on_device = 0 when
+ * the contract sent the array to the host route */
+int fwgpu_debug_quantize(int device, const float *weights, uint64_t n, uint8_t *out, uint64_t cap, int *on_device);
+/* debug (scripts/bench_publish.py): milliseconds, by device events, of the statistics kernels, the bucket kernel and a device-to-device copy
+ * of the same table, on the regressor's FFM weights; nothing of the regressor changes */
+int fwgpu_debug_quantize_rates(fwgpu_regressor *r, float *ms3);
 /* --convert_inference_regressor (main.rs:136-148): training file -> inference file; host only */
 int fwgpu_model_convert_inference(const char *in_path, const char *out_path, int quantize_weights);
 /* quantization.rs:42-98: out = 8-byte header {f32 increment, f32 min} + n f16 bucket numbers (8 + 2n bytes) */
