@@ -6,4 +6,4 @@ fails loudly if the library has not been built or no GPU is present."""
 from . import _capi as capi  # noqa: F401
 from .regressor import (Batch, BlockCache, SplitBuffers, FeatureBuffer, FeatureBufferTranslator, FeatureComboDesc, HogwildTrainer,  # noqa: F401
                         ModelInstance, NamespaceDescriptor, Optimizer, Regressor, ffm_vec, lr_and_ffm_vec, lr_vec,
-                        synth_records, Trainer, binned_auc, debug_metrics)
+                        synth_records, Trainer, binned_auc, debug_metrics, debug_delay_plan)

@@ -200,6 +200,9 @@ def lib():
         "fwgpu_trainer_examples_seen": [vp, P(u64)],
         "fwgpu_trainer_set_holdout": [vp, u64, i32],
         "fwgpu_trainer_predictions": [vp, vp, u64, P(u64)],
+        "fwgpu_trainer_set_delay": [vp, u64, u64],
+        "fwgpu_trainer_delay_state": [vp, P(u64), P(u64), P(u64), P(u64)],
+        "fwgpu_debug_delay_plan": [vp, u32, u64, vp],
         "fwgpu_batch_metrics": [vp, u32, u32, i32, vp, vp, vp],
         "fwgpu_trainer_set_metrics": [vp, u64],
         "fwgpu_trainer_metrics": [vp, vp, u64, P(u64), vp, vp],

@@ -98,5 +98,8 @@ hipError_t text_host_lines(const uint4 *status, uint32_t nlines, uint32_t *host_
 // win_stats[kTextPlanStats * n_windows]; host_off[j] = rec_off[host_lines[j]] for the first n_host listed lines (0 for a line beyond n_take)
 hipError_t text_batch_plan(const uint4 *status, uint32_t n_take, uint32_t micro_batch, uint32_t learn_before, uint64_t *rec_off, uint64_t *win_stats,
                            const uint32_t *host_lines, uint32_t n_host, uint64_t *host_off, void *tmp, size_t tmp_bytes, hipStream_t stream);
+// A launch window's offsets rebased to a copy of its records alone (the delayed protocol's ring, trainer.cpp): rec_off_first = rec_off + first of the
+// piece's plan, out[i] = rec_off[first + i] - rec_off[first] for i = 0 .. n (n + 1 entries; out holds at least that many)
+hipError_t text_window_offsets(const uint64_t *rec_off_first, uint32_t n, uint64_t *out, hipStream_t stream);
 
 }  // namespace fwgpu

@@ -520,7 +520,19 @@ __global__ void text_plan_host_off(const uint64_t *rec_off, uint32_t n_take, con
     host_off[j] = line < n_take ? rec_off[line] : 0ull;
 }
 
+// a launch window's offsets for a copy of its records that starts at word 0: lane i reads one entry, every lane the window's first (a broadcast)
+__global__ void text_window_offsets_kernel(const uint64_t *rec_off, uint32_t n_off, uint64_t *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_off) out[i] = rec_off[i] - rec_off[0];
+}
+
 }  // namespace
+
+hipError_t text_window_offsets(const uint64_t *rec_off_first, uint32_t n, uint64_t *out, hipStream_t stream) {
+    const uint32_t n_off = n + 1;
+    text_window_offsets_kernel<<<(n_off + 255) / 256, 256, 0, stream>>>(rec_off_first, n_off, out);
+    return hipGetLastError();
+}
 
 size_t text_plan_temp_bytes(uint32_t nlines_max) {
     size_t a = 0, b = 0;

@@ -8,6 +8,7 @@
 #include <string>
 
 #include <algorithm>
+#include <deque>
 #include <memory>
 #include <chrono>
 #include <thread>
@@ -60,7 +61,24 @@ struct fwgpu_trainer {
     fwgpu_batch *text_tr = nullptr;
     // progressive / hold-out loss (fwgpu_trainer_set_metrics; metrics.hip): window 0 = off, nothing below is touched
     MetricsTable metrics;
+    // delayed protocol (fwgpu_trainer_set_delay; main.rs:248-258): delay 0 = off, nothing below is touched.  A launch window's record batch stays in
+    // device memory between its predict launch and its learn launch: `pending` in stream order, learned ones in `spare` for the next windows.
+    struct RingBatch {
+        fwgpu_batch *b = nullptr;
+        hipEvent_t learned = nullptr;  // the batch's learn launch has run: it may be refilled
+        uint64_t last = 0;             // stream number of the window's last example
+        uint32_t n = 0;
+    };
+    uint64_t delay = 0, predictions_after = 0;
+    std::deque<RingBatch> pending, spare;
+    uint64_t learned_through = 0, pending_examples = 0, ring_bytes = 0;
 };
+
+// The delayed protocol's eligibility rule, the one copy of it: once the window that ends at example `taken_last` has been taken, a pending window that
+// ends at `pending_last` is learned iff pending_last <= taken_last - delay.
+static bool delay_eligible(uint64_t pending_last, uint64_t taken_last, uint64_t delay) {
+    return taken_last >= delay && pending_last <= taken_last - delay;
+}
 
 static bool predict_mode(const fwgpu_trainer *tr) {  // for the NEXT example (number seen + 1)
     return tr->testonly || (tr->holdout_after && tr->seen + 1 >= tr->holdout_after);
@@ -116,18 +134,26 @@ static int stage_slot(fwgpu_trainer *tr, int c, uint32_t n) {
 
 // second half, shared by the host-fed and the device text route: slot c's launches are on the compute stream; the predictions of its n_pred
 // examples that were not learned (d_pred, NULL: none) come back with them, the slot's event closes it and the other slot is the current one
-static int close_slot(fwgpu_trainer *tr, int c, const float *d_pred, uint32_t n_pred) {
+// slot c's pinned prediction buffer holds n_pred floats (the slot is retired: nothing in flight writes the old one)
+static int reserve_pred_host(fwgpu_trainer *tr, int c, uint32_t n_pred) {
+    if (tr->pred_cap[c] >= n_pred) return FWGPU_OK;
+    if (tr->pred_host[c]) (void)hipHostFree(tr->pred_host[c]);
+    tr->pred_host[c] = nullptr;
+    tr->pred_cap[c] = 0;
+    FWGPU_HIP(hipHostMalloc((void **)&tr->pred_host[c], (size_t)std::max(n_pred, tr->micro_batch) * 4, hipHostMallocDefault));
+    tr->pred_cap[c] = std::max(n_pred, tr->micro_batch);
+    return FWGPU_OK;
+}
+
+// (`gathered`: the caller's launches have already left the n_pred predictions in the slot's pinned buffer, window by window)
+static int close_slot(fwgpu_trainer *tr, int c, const float *d_pred, uint32_t n_pred, bool gathered = false) {
+    if (gathered) d_pred = nullptr;
     if (d_pred && n_pred) {
-        if (tr->pred_cap[c] < n_pred) {
-            if (tr->pred_host[c]) (void)hipHostFree(tr->pred_host[c]);
-            tr->pred_host[c] = nullptr;
-            tr->pred_cap[c] = 0;
-            FWGPU_HIP(hipHostMalloc((void **)&tr->pred_host[c], (size_t)std::max(n_pred, tr->micro_batch) * 4, hipHostMallocDefault));
-            tr->pred_cap[c] = std::max(n_pred, tr->micro_batch);
-        }
+        int rc = reserve_pred_host(tr, c, n_pred);
+        if (rc) return rc;
         FWGPU_HIP(hipMemcpyAsync(tr->pred_host[c], d_pred, (size_t)n_pred * 4, hipMemcpyDeviceToHost, tr->stream));
     }
-    tr->slot_predict[c] = d_pred && n_pred;
+    tr->slot_predict[c] = (d_pred || gathered) && n_pred;
     tr->slot_n[c] = n_pred;
     FWGPU_HIP(hipEventRecord(tr->done[c], tr->stream));
     tr->in_flight[c] = true;
@@ -147,10 +173,112 @@ static int open_slot(fwgpu_trainer *tr) {
     return FWGPU_OK;
 }
 
+// ---- delayed protocol: the ring of record batches between a window's predict launch and its learn launch
+// A batch for a window of n examples / `words` record words: a learned batch that is large enough (its learn launch waited for: long past in steady
+// state), else a new allocation; a learned batch that is too small makes room for it.  No allocation once the ring has reached its size.
+static int ring_take(fwgpu_trainer *tr, uint32_t n, uint64_t words, fwgpu_trainer::RingBatch *out) {
+    for (auto it = tr->spare.begin(); it != tr->spare.end(); ++it) {
+        if (it->b->n_cap < n || it->b->words_cap < words) continue;
+        *out = *it;
+        tr->spare.erase(it);
+        FWGPU_HIP(hipEventSynchronize(out->learned));
+        return FWGPU_OK;
+    }
+    if (!tr->spare.empty()) {  // (none fits: the oldest one goes; hipFree waits for the device)
+        tr->ring_bytes -= tr->spare.front().b->dev_bytes;
+        fwgpu_batch_free(tr->spare.front().b);
+        (void)hipEventDestroy(tr->spare.front().learned);
+        tr->spare.pop_front();
+    }
+    fwgpu_trainer::RingBatch rb;
+    const uint32_t n_cap = std::max(n, tr->micro_batch);
+    const uint64_t words_cap = words * 3 / 2 + 4096;
+    int rc = record_batch_alloc(tr->r, &tr->t, n_cap, words_cap, &rb.b);
+    if (rc == FWGPU_OK && hipEventCreateWithFlags(&rb.learned, hipEventDisableTiming) != hipSuccess) {
+        fwgpu_batch_free(rb.b);
+        rc = fail(FWGPU_ERR_DEVICE, "hipEventCreateWithFlags");
+    }
+    if (rc) {
+        (void)hipGetLastError();
+        const std::string why = fwgpu_last_error();
+        return fail(FWGPU_ERR_DEVICE, "prediction_model_delay: no device memory for a window of " + std::to_string(n_cap) + " examples / " +
+                                          std::to_string(words_cap) + " record words; the ring holds " + std::to_string(tr->ring_bytes) + " bytes, " +
+                                          std::to_string(tr->pending.size()) + " windows (" + std::to_string(tr->pending_examples) + " examples) pending (" + why + ")");
+    }
+    tr->ring_bytes += rb.b->dev_bytes;
+    *out = rb;
+    return FWGPU_OK;
+}
+
+// the window in `rb` (records in place, on the compute stream) ends at stream number `last`: its predict-only launch if its examples are predicted,
+// scored as examples that will be learned; then it is pending
+static int ring_predict_and_keep(fwgpu_trainer *tr, fwgpu_trainer::RingBatch rb, uint64_t last, bool predicted) {
+    rb.n = rb.b->n;
+    rb.last = last;
+    tr->pending.push_back(rb);  // (first: whatever fails below, the batch is the ring's)
+    tr->pending_examples += rb.n;
+    if (!predicted) return FWGPU_OK;
+    int rc = fwgpu_learn_batch(tr->r, rb.b, FWGPU_MODE_HOGWILD, 0, tr->stream);
+    if (rc) return rc;
+    return score_launch(tr, rb.b, last - rb.n + 1, true);
+}
+
+// every pending window that the window ending at `taken_last` makes eligible is learned, oldest first (not scored: an example counts once)
+static int ring_learn_eligible(fwgpu_trainer *tr, uint64_t taken_last) {
+    while (!tr->pending.empty() && delay_eligible(tr->pending.front().last, taken_last, tr->delay)) {
+        fwgpu_trainer::RingBatch rb = tr->pending.front();
+        int rc = fwgpu_learn_batch(tr->r, rb.b, FWGPU_MODE_HOGWILD, 1, tr->stream);
+        if (rc) return rc;
+        FWGPU_HIP(hipEventRecord(rb.learned, tr->stream));
+        tr->pending.pop_front();
+        tr->pending_examples -= rb.n;
+        tr->learned_through = rb.last;
+        tr->spare.push_back(rb);
+    }
+    return FWGPU_OK;
+}
+
+// flush in the delayed protocol: the staged window goes up into a ring batch, is predicted there and stays; then the windows it makes eligible are learned
+static int flush_delayed(fwgpu_trainer *tr) {
+    const int c = tr->cur;
+    const uint32_t n = (uint32_t)(tr->off[c].size() - 1);
+    fwgpu_regressor *r = tr->r;
+    FWGPU_HIP(hipSetDevice(r->device));
+    int rc = retire(tr, c);  // (the slot's pinned prediction buffer)
+    if (rc) return rc;
+    fwgpu_trainer::RingBatch rb;
+    if ((rc = ring_take(tr, n, tr->rec_used[c], &rb))) {  // the window is dropped: the trainer stays usable for fwgpu_finish / fwgpu_trainer_free
+        tr->seen -= n;
+        tr->rec_used[c] = 0;
+        tr->off[c].assign(1, 0);
+        tr->stats[c] = RecordStats();
+        return rc;
+    }
+    const uint64_t last = tr->seen;  // (`seen` already counts the staged examples)
+    const bool predicted = last - n + 1 > tr->predictions_after;
+    rc = record_batch_upload(rb.b, &tr->t, tr->rec[c], tr->off[c].data(), n, tr->copy_stream, &tr->stats[c]);
+    // an oversize example's host copy stays with its batch: both visits take the chunked route
+    if (rc == FWGPU_OK) rc = record_batch_host_copy_if_oversize(r, &tr->t, rb.b, tr->rec[c], tr->off[c].data(), n);
+    if (rc == FWGPU_OK && hipEventRecord(tr->uploaded[c], tr->copy_stream) != hipSuccess) rc = fail(FWGPU_ERR_DEVICE, "hipEventRecord");
+    if (rc == FWGPU_OK && hipStreamWaitEvent(tr->stream, tr->uploaded[c], 0) != hipSuccess) rc = fail(FWGPU_ERR_DEVICE, "hipStreamWaitEvent");
+    if (rc) {  // (nothing reads the batch: it is a spare one again)
+        (void)hipStreamSynchronize(tr->copy_stream);
+        (void)hipEventRecord(rb.learned, tr->stream);
+        tr->spare.push_back(rb);
+        return rc;
+    }
+    if ((rc = ring_predict_and_keep(tr, rb, last, predicted))) return rc;
+    // the staging buffer and the predictions close with the predict launch; the learn launches read ring batches only
+    if ((rc = close_slot(tr, c, predicted ? rb.b->pred : nullptr, n))) return rc;
+    if ((rc = ring_learn_eligible(tr, last))) return rc;
+    return open_slot(tr);
+}
+
 static int flush(fwgpu_trainer *tr, bool predict = false) {
     const int c = tr->cur;
     const uint32_t n = (uint32_t)(tr->off[c].size() - 1);
     if (n == 0) return FWGPU_OK;
+    if (tr->delay) return flush_delayed(tr);
     fwgpu_regressor *r = tr->r;
     FWGPU_HIP(hipSetDevice(r->device));
     int rc = stage_slot(tr, c, n);
@@ -221,6 +349,71 @@ static int launch_text_piece(fwgpu_trainer *tr, fwgpu_text_parser *tp, int c, co
     return close_slot(tr, c, n_pred ? P.d_pred + P.n_learn : nullptr, n_pred);
 }
 
+// launch_text_piece in the delayed protocol.  The parser's buffers are reused two pieces later, so every window's records are copied device to device
+// into a ring batch on the compute stream, its offsets rebased to the copy (textparse.hip text_window_offsets), and the launches read the copy.  The plan
+// was cut at predictions_after: its windows [0, n_windows_learn) hold the examples that are not predicted.
+static int launch_text_piece_delayed(fwgpu_trainer *tr, fwgpu_text_parser *tp, int c, const TextTrainPiece &P) {
+    fwgpu_regressor *r = tr->r;
+    FWGPU_HIP(hipEventRecord(tr->uploaded[c], text_train_stream(tp)));
+    FWGPU_HIP(hipStreamWaitEvent(tr->stream, tr->uploaded[c], 0));
+    TextPlanShape shape;
+    shape.n_learn = P.n_learn;
+    shape.n_windows_learn = P.n_windows_learn;
+    shape.n_windows = P.n_windows;
+    const uint32_t n_pred = P.n_take - P.n_learn;
+    int rc = reserve_pred_host(tr, c, n_pred);
+    if (rc) return rc;
+    uint64_t word0 = 0;  // the piece's records lie back to back in window order (text_batch_plan: rec_off is the running sum of the lines' lengths)
+    for (uint32_t w = 0; w < P.n_windows; w++) {
+        const uint64_t *st = P.win_stats + (size_t)kTextPlanStats * w;
+        uint32_t first, end;
+        shape.window(w, tr->micro_batch, P.n_take, &first, &end);
+        const uint32_t n = end - first;
+        if (st[0] != n || word0 + st[1] > P.n_words) return fail(FWGPU_ERR_DEVICE, "training from text: the plan's windows are not the host's");
+        fwgpu_trainer::RingBatch rb;
+        if ((rc = ring_take(tr, n, st[1], &rb))) return rc;
+        fwgpu_batch *b = rb.b;
+        hipError_t e = st[1] ? hipMemcpyAsync(b->records, P.d_records + word0, 4 * (size_t)st[1], hipMemcpyDeviceToDevice, tr->stream) : hipSuccess;
+        if (e == hipSuccess) e = text_window_offsets(P.d_rec_off + first, n, b->rec_off, tr->stream);
+        if (e != hipSuccess) {
+            (void)hipEventRecord(rb.learned, tr->stream);
+            tr->spare.push_back(rb);
+            return fail(FWGPU_ERR_DEVICE, std::string("training from text: copying a window into the delay ring: ") + hipGetErrorString(e));
+        }
+        word0 += st[1];
+        b->n = n;
+        b->n_lr = st[5];
+        b->n_ffm = st[6];
+        b->n_words = st[1];
+        b->max_lr = r->cfg.wiring == FWGPU_WIRING_FFM_ONLY ? 0 : (uint32_t)st[2];  // as record_batch_upload leaves a batch
+        b->max_ffm = (uint32_t)st[3];
+        b->max_rec = (uint32_t)st[4];
+        b->aligned4 = true;
+        b->host_copy.reset();
+        if (record_batch_is_oversize(b)) {  // the one read-back: the host's translation of the window stays with the batch for both visits
+            std::vector<uint64_t> off((size_t)n + 1);
+            std::vector<uint32_t> words((size_t)st[1]);
+            e = hipStreamSynchronize(tr->stream);
+            if (e == hipSuccess) e = hipMemcpy(off.data(), b->rec_off, 8 * off.size(), hipMemcpyDeviceToHost);
+            if (e == hipSuccess && !words.empty()) e = hipMemcpy(words.data(), b->records, 4 * words.size(), hipMemcpyDeviceToHost);
+            rc = e != hipSuccess ? fail(FWGPU_ERR_DEVICE, std::string("training from text: reading an oversize window back: ") + hipGetErrorString(e))
+                 : off[0] != 0 || off.back() != st[1] ? fail(FWGPU_ERR_DEVICE, "training from text: a window's offsets and its word count differ")
+                                                      : record_batch_host_copy_if_oversize(r, &tr->t, b, words.data(), off.data(), n);
+            if (rc) {
+                (void)hipEventRecord(rb.learned, tr->stream);
+                tr->spare.push_back(rb);
+                return rc;
+            }
+        }
+        const uint64_t last = tr->seen + end;  // (`seen` counts the piece once it is launched)
+        const bool predicted = w >= P.n_windows_learn;
+        if ((rc = ring_predict_and_keep(tr, rb, last, predicted))) return rc;
+        if (predicted) FWGPU_HIP(hipMemcpyAsync(tr->pred_host[c] + (first - P.n_learn), b->pred, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream));
+        if ((rc = ring_learn_eligible(tr, last))) return rc;
+    }
+    return close_slot(tr, c, nullptr, n_pred, true);
+}
+
 extern "C" {
 
 int fwgpu_trainer_create(fwgpu_regressor *r, const fwgpu_translator_config *t, uint32_t micro_batch, fwgpu_trainer **out) {
@@ -275,6 +468,8 @@ int fwgpu_digest_records(fwgpu_trainer *tr, const uint32_t *records, const uint6
             const uint64_t until = tr->holdout_after - 1 - tr->seen;  // examples that may still be learned (>= 1 here)
             if (take > until) take = (uint32_t)until;
         }
+        if (tr->delay && tr->seen < tr->predictions_after)  // ... nor predictions_after: a window's examples are predicted, or none is
+            take = (uint32_t)std::min<uint64_t>(take, tr->predictions_after - tr->seen);
         // the records are copied (main.rs:243 `Vec::from(buffer)`)
         const uint64_t w0 = rec_off[i], w1 = rec_off[i + take];
         const uint64_t base = tr->rec_used[c];
@@ -311,7 +506,7 @@ int fwgpu_digest_records(fwgpu_trainer *tr, const uint32_t *records, const uint6
         for (uint32_t j = 1; j <= take; j++) tr->off[c].push_back(base + (rec_off[i + j] - w0));
         tr->seen += take;
         i += take;
-        if (tr->off[c].size() - 1 >= tr->micro_batch || (!predicting && predict_mode(tr))) {
+        if (tr->off[c].size() - 1 >= tr->micro_batch || (!predicting && predict_mode(tr)) || (tr->delay && tr->seen == tr->predictions_after)) {
             int rc = flush(tr, predicting);  // the last learned example closes its micro-batch
             if (rc) return rc;
         }
@@ -585,6 +780,8 @@ int fwgpu_trainer_digest_text_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, f
         uint32_t learn_before = kTextNoHoldout;  // lines of this piece that may still be learned: no launch straddles the hold-out boundary
         if (tr->testonly) learn_before = 0;
         else if (tr->holdout_after) learn_before = (uint32_t)std::min<uint64_t>(tr->seen + 1 >= tr->holdout_after ? 0 : tr->holdout_after - 1 - tr->seen, 0xfffffffeu);
+        else if (tr->delay)  // delayed protocol: nothing is held out; the plan's cut is the one at predictions_after (lines before it are not predicted)
+            learn_before = (uint32_t)std::min<uint64_t>(tr->seen >= tr->predictions_after ? 0 : tr->predictions_after - tr->seen, 0xfffffffeu);
         TextTrainPiece P;
         if ((rc = text_train_piece(tp, text + pos, cut, c, tr->micro_batch, learn_before, &P))) return rc;
         if (P.n_take) {
@@ -594,7 +791,7 @@ int fwgpu_trainer_digest_text_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, f
                 FWGPU_HIP(hipMemcpy(back.data(), P.d_records, 4 * back.size(), hipMemcpyDeviceToHost));
                 if ((rc = fwgpu_cache_push_records(cache, back.data(), P.n_words))) return rc;
             }
-            if ((rc = launch_text_piece(tr, tp, c, P))) return rc;
+            if ((rc = tr->delay ? launch_text_piece_delayed(tr, tp, c, P) : launch_text_piece(tr, tp, c, P))) return rc;
             if ((rc = open_slot(tr))) return rc;  // (waits for the piece BEFORE this one, whose buffers the next piece takes)
             tr->seen += P.n_take;
             done += P.n_take;
@@ -615,8 +812,44 @@ int fwgpu_trainer_digest_text_device(fwgpu_trainer *tr, fwgpu_text_parser *tp, f
 int fwgpu_trainer_set_holdout(fwgpu_trainer *tr, uint64_t holdout_after, int testonly) {
     if (!tr) return fail(FWGPU_ERR_INVALID, "NULL trainer");
     if (tr->off[tr->cur].size() > 1) return fail(FWGPU_ERR_INVALID, "set the hold-out before digesting (or right after fwgpu_finish)");
+    if (tr->delay && (holdout_after || testonly))
+        return fail(FWGPU_ERR_INVALID, std::string("set_holdout: ") + (testonly ? "testonly" : "holdout_after") +
+                                           " conflicts with prediction_model_delay (fwgpu_trainer_set_delay), whose loop holds nothing out: set one of them");
     tr->holdout_after = holdout_after;
     tr->testonly = testonly != 0;
+    return FWGPU_OK;
+}
+
+int fwgpu_trainer_set_delay(fwgpu_trainer *tr, uint64_t delay, uint64_t predictions_after) {
+    if (!tr) return fail(FWGPU_ERR_INVALID, "NULL trainer");
+    if (tr->seen) return fail(FWGPU_ERR_INVALID, "set_delay: prediction_model_delay and predictions_after are set before the first example is digested");
+    if (delay && (tr->holdout_after || tr->testonly))
+        return fail(FWGPU_ERR_INVALID, std::string("set_delay: prediction_model_delay conflicts with ") + (tr->testonly ? "testonly" : "holdout_after") +
+                                           " (fwgpu_trainer_set_holdout): the delayed loop holds nothing out: set one of them");
+    tr->delay = delay;
+    tr->predictions_after = delay ? predictions_after : 0;
+    return FWGPU_OK;
+}
+
+int fwgpu_trainer_delay_state(const fwgpu_trainer *tr, uint64_t *learned_through, uint64_t *pending_examples, uint64_t *pending_windows, uint64_t *ring_bytes) {
+    if (!tr) return fail(FWGPU_ERR_INVALID, "NULL trainer");
+    if (learned_through) *learned_through = tr->learned_through;
+    if (pending_examples) *pending_examples = tr->pending_examples;
+    if (pending_windows) *pending_windows = tr->pending.size();
+    if (ring_bytes) *ring_bytes = tr->ring_bytes;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_delay_plan(const uint64_t *window_last, uint32_t n_windows, uint64_t delay, uint64_t *learned_through_after) {
+    if (n_windows && (!window_last || !learned_through_after)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (!delay) return fail(FWGPU_ERR_INVALID, "delay_plan: delay must be > 0 (0 is the trainer without the delayed protocol)");
+    uint64_t learned = 0;
+    uint32_t front = 0;  // oldest pending window
+    for (uint32_t j = 0; j < n_windows; j++) {
+        if (window_last[j] <= (j ? window_last[j - 1] : 0)) return fail(FWGPU_ERR_INVALID, "delay_plan: the windows' last numbers must grow, from 1");
+        while (front <= j && delay_eligible(window_last[front], window_last[j], delay)) learned = window_last[front++];
+        learned_through_after[j] = learned;
+    }
     return FWGPU_OK;
 }
 
@@ -666,6 +899,11 @@ int fwgpu_trainer_free(fwgpu_trainer *tr) {
     (void)hipSetDevice(tr->r->device);
     if (tr->stream) (void)hipStreamSynchronize(tr->stream);
     if (tr->text_tr) fwgpu_batch_free(tr->text_tr);
+    for (std::deque<fwgpu_trainer::RingBatch> *q : {&tr->pending, &tr->spare})  // the delay ring: pending windows are dropped unlearned, like the reference's queue
+        for (fwgpu_trainer::RingBatch &rb : *q) {
+            fwgpu_batch_free(rb.b);
+            (void)hipEventDestroy(rb.learned);
+        }
     tr->metrics.release();
     for (int i = 0; i < 2; i++) {
         if (tr->dev[i]) fwgpu_batch_free(tr->dev[i]);

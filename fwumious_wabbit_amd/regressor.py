@@ -648,6 +648,18 @@ class HogwildTrainer:
         """main.rs:184-185, 238-241: examples numbered >= holdout_after (from 1), or all with testonly, are predicted, not learned"""
         check(capi.lib().fwgpu_trainer_set_holdout(self.h, holdout_after, int(testonly)))
 
+    def set_delay(self, delay, predictions_after=0):
+        """`--prediction_model_delay` (main.rs:248-258): example i is predicted by a model that has learned nothing newer than example
+        i - 1 - delay, then learned `delay` examples later (fwgpu.h states the window rule and its bounds); 0 = off.  Examples numbered
+        <= predictions_after get no prediction.  Before the first example is digested; conflicts with set_holdout."""
+        check(capi.lib().fwgpu_trainer_set_delay(self.h, delay, predictions_after))
+
+    def delay_state(self):
+        """the delayed protocol's ring: dict(learned_through, pending_examples, pending_windows, ring_bytes)"""
+        v = [C.c_uint64() for _ in range(4)]
+        check(capi.lib().fwgpu_trainer_delay_state(self.h, *(C.byref(x) for x in v)))
+        return dict(zip(("learned_through", "pending_examples", "pending_windows", "ring_bytes"), (x.value for x in v)))
+
     def predictions(self) -> np.ndarray:
         """predictions of the examples that were not learned, in stream order (call after block_until_workers_finished)"""
         n = C.c_uint64()
@@ -737,6 +749,15 @@ class HogwildTrainer:
 
 
 Trainer = HogwildTrainer
+
+
+def debug_delay_plan(window_last, delay):
+    """the delayed protocol's eligibility rule alone (fwgpu_debug_delay_plan, no device): the windows' last example numbers -> the last
+    example number learned after each window's step"""
+    last = np.ascontiguousarray(window_last, dtype=np.uint64)
+    out = np.zeros(len(last), dtype=np.uint64)
+    check(capi.lib().fwgpu_debug_delay_plan(ptr(last), len(last), delay, ptr(out)))
+    return out
 
 
 def debug_metrics(pred, label, importance, learned, first_number, window, launch=0, stream=None):

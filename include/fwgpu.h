@@ -399,6 +399,52 @@ int fwgpu_trainer_examples_seen(const fwgpu_trainer *tr, uint64_t *n);
 int fwgpu_trainer_set_holdout(fwgpu_trainer *tr, uint64_t holdout_after, int testonly);
 int fwgpu_trainer_predictions(fwgpu_trainer *tr, float *out, uint64_t cap, uint64_t *n);
 
+/* ---------------------------------------------------------------- predicting with a model delayed by N examples
+ * `--prediction_model_delay N` (cmdline.rs:284-289, main.rs:200-258): labels arrive late, so example i (from 1) is predicted by a model
+ * that has learned nothing newer than example i - 1 - N.  The reference's loop for N > 0:
+ *     if i > predictions_after: prediction = learn(example i, update = false)
+ *     push example i;  if the queue is longer than N: pop the oldest (example i - N) and learn it
+ * and at the end of input the queue is dropped: the last N examples are never learned.
+ *
+ * fwgpu_trainer_set_delay: delay == 0 (the default) leaves the trainer what it is without this call -- same launches, same bits;
+ *   delay > 0 turns the delayed protocol on for every route (fwgpu_digest_records, _digest_cache, _digest_text, _digest_file and the
+ *   device text route).  FWGPU_ERR_INVALID once examples have been digested, and together with holdout_after > 0 or testonly in either
+ *   call order (fwgpu_trainer_set_holdout refuses likewise while a delay is set): the reference's command line declares that conflict
+ *   and its delayed loop ignores holdout_after; this library refuses instead of ignoring.
+ *
+ * The window rule.  The trainer works in launch windows: a window holds at most micro_batch consecutive examples, no window straddles
+ * predictions_after, fwgpu_finish closes a partial one (the device text route also closes one at the end of every piece of text).  When
+ * the window that ends at example e has been taken:
+ *   1. if its examples are numbered > predictions_after, a predict-only launch scores it (update = 0, FWGPU_MODE_HOGWILD, the route
+ *      fwgpu_learn_batch picks);
+ *   2. those predictions are appended to the list fwgpu_trainer_predictions returns, in stream order;
+ *   3. its record batch joins a ring in device memory: records do not come back to the host for their second visit;
+ *   4. every pending window whose LAST example is numbered <= e - delay is learned, oldest first, one learn launch each, on the same
+ *      stream, and leaves the ring.
+ * Nothing else learns.  Hence, for every predicted example i:
+ *   - its model has learned NO example numbered above i - 1 - delay: it is never fresher than the reference's;
+ *   - its model has learned every example up to i - 1 - delay - (2 * micro_batch - 2) at least;
+ *   - with micro_batch == 1 the trainer IS the reference's loop.
+ * After fwgpu_finish the pending windows stay pending -- at least `delay` examples are unlearned (all of them, if fewer were digested),
+ * like the reference at the end of input -- and the trainer stays usable: further digests continue the same stream and the same ring.
+ * fwgpu_trainer_free drops the ring.
+ *
+ * The ring holds about delay + 2 * micro_batch examples' records.  Learned batches are refilled, so a steady stream allocates nothing.
+ * A failed allocation is FWGPU_ERR_DEVICE with the sizes in the message; that window is dropped (fwgpu_trainer_examples_seen does not
+ * count it) and the trainer stays usable for fwgpu_finish / fwgpu_trainer_free.  A window with an oversize example keeps the host's
+ * translation with its batch and takes the example-by-example route on both visits.
+ * Metrics (fwgpu_trainer_set_metrics): a window's predict launch is scored on the LEARNED side -- progressive predictions of examples
+ * that will be learned; its later learn launch is not scored (an example counts once); examples <= predictions_after are not scored.
+ *
+ * fwgpu_trainer_delay_state (any pointer may be NULL): the last example number learned (0: none), the examples and windows pending in
+ *   the ring (an open micro-batch still on the host is not among them), and the bytes of device memory the ring's batches take.
+ * fwgpu_debug_delay_plan: the eligibility rule alone, on the host: given the windows' last example numbers (growing, from 1) and a
+ *   delay > 0, learned_through_after[j] = the last example number learned once window j's step is done (0: none yet). */
+int fwgpu_trainer_set_delay(fwgpu_trainer *tr, uint64_t delay, uint64_t predictions_after);
+int fwgpu_trainer_delay_state(const fwgpu_trainer *tr, uint64_t *learned_through, uint64_t *pending_examples, uint64_t *pending_windows,
+                              uint64_t *ring_bytes);
+int fwgpu_debug_delay_plan(const uint64_t *window_last, uint32_t n_windows, uint64_t delay, uint64_t *learned_through_after);
+
 /* ---------------------------------------------------------------- progressive and hold-out loss, scored on the device
  * The reference's example loop has a prediction for every example, made BEFORE the example is learned (main.rs:246) and written out
  * (main.rs:260-268); the loss of those predictions is benchmark/calc_loss.py's.  Here a kernel (csrc/metrics.hip) scores the
