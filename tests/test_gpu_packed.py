@@ -340,3 +340,61 @@ def test_serving_ffi_with_packed_weights(tmp_path):
     cl.close()
     pr.close()
     rp.close()
+
+
+# ------------------------------------------------------------------ 10. every shape the packed form accepts, per example against float64
+PACKED_SHAPES = [(6, 4), (30, 8),                        # one chunk
+                 (20, 12), (21, 12), (12, 20), (10, 24),  # k no power of two: a real division in the packed gather; 21 x 12: the last lane partly filled
+                 (8, 32), (2, 128),                      # a full single chunk (256 buckets)
+                 (16, 32), (4, 128), (5, 64),            # two chunks: full, full, nearly empty (320 buckets)
+                 (30, 16), (40, 8)]                      # shapes the stream tests run
+
+
+@pytest.mark.parametrize("F,k", PACKED_SHAPES, ids=[f"{F}x{k}" for F, k in PACKED_SHAPES])
+def test_packed_predictions_per_example_against_float64(F, k):
+    """Regressor.pack() of the shape's warm state (tests/ffm_ref.py: probe_stream, warm_state, as test_gpu_ffm_step.py's predict-only case), then
+    predict-only launches of the packed regressor from entry and record batches, concurrent and in order: every prediction within
+    min(C_P * M_p + 4 ulp, 5e-5) of the float64 forward pass (ffm_ref.judge_prediction) on the values the buckets stand for -- the packed
+    regressor's own table_read -- and the source's LR table."""
+    from types import SimpleNamespace
+
+    import ffm_ref
+    from helpers import check_disjoint, disjoint_models
+
+    st = ffm_ref.probe_stream(F, k)
+    mi, _, _ = disjoint_models(st, ffm_ref.LUT)
+    check_disjoint(st, mi)
+    re = fw.Regressor(mi)
+    rp = None
+    try:
+        for t, v in zip((capi.TABLE_FFM_W, capi.TABLE_FFM_ACC, capi.TABLE_LR), ffm_ref.warm_state(st)):
+            re.table_write(t, v)
+        rp = re.pack()
+        assert rp.ffm_storage()[0] == capi.FFM_F16_BUCKETS
+        w, lr = rp.table_read(capi.TABLE_FFM_W), re.table_read(capi.TABLE_LR)
+        assert np.array_equal(_bits(rp.table_read(capi.TABLE_LR)[0::2]), _bits(lr[0::2]))  # (the weights; an immutable regressor keeps no accumulators)
+        assert not np.array_equal(_bits(w), _bits(re.table_read(capi.TABLE_FFM_W)))  # (the buckets' values, not the source's)
+        cfg = SimpleNamespace(F=F, k=k)
+        ref = [ffm_ref.predict(cfg, w, lr, fb.lr_buffer, fb.ffm_buffer) for fb in st.fbs]
+        assert np.std([r[0] for r in ref]) > 0.02  # (a model that says something)
+        fbt = fw.FeatureBufferTranslator(rp.mi)
+        for route in ("entries", "records"):
+            b = rp.batch(st.fbs) if route == "entries" else rp.record_batch(fbt, st.recs, st.off)
+            try:
+                for mode in (capi.MODE_HOGWILD, capi.MODE_SEQUENTIAL):
+                    rp.learn_batch(b, mode, False)
+                    info = rp.last_launch()
+                    assert info["family"] == capi.KERNEL_PACKED and info["chunks"] == (1 if F * k <= 256 else 2), info
+                    p = b.predictions().copy()
+                    worst = 0.0
+                    for e in range(st.n):
+                        err, bound, need = ffm_ref.judge_prediction(p[e], *ref[e])
+                        worst = max(worst, need)
+                        assert err <= bound, (route, mode, e, float(p[e]), ref[e], err, bound, need, ffm_ref.C_P)
+                    print(f"PACKEDPREDICT {F}x{k} {route} mode {mode}: needs c_p = {worst:.3e} = {worst / ffm_ref.C_P:.3f} C_P")
+            finally:
+                b.close()
+    finally:
+        if rp is not None:
+            rp.close()
+        re.close()
