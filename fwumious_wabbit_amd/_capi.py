@@ -23,9 +23,9 @@ WIRING_REGRESSOR, WIRING_FFM_ONLY = 0, 1
 MODE_SEQUENTIAL, MODE_HOGWILD = 0, 1
 TABLE_LR, TABLE_FFM_W, TABLE_FFM_ACC, TABLE_NN_W, TABLE_NN_ACC = 0, 1, 2, 3, 4
 # fwgpu_debug_last_route
-ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK = 0, 1, 2, 3, 4, 5
+ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK, ROUTE_REQUESTS = 0, 1, 2, 3, 4, 5, 6
 # fwgpu_debug_last_launch
-KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED = 0, 1, 2, 3
+KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED, KERNEL_REQUESTS = 0, 1, 2, 3, 4
 LAUNCH_INFO = ("family", "chunks", "window", "chain", "no_kept_rows", "lds_keep", "threads", "lds_bytes")
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
@@ -141,6 +141,7 @@ def lib():
         "fwgpu_block_cache_cover_record": [vp, P(TranslatorConfig), vp, u32],
         "fwgpu_block_cache_record_ok": [vp, P(TranslatorConfig), vp, u32],
         "fwgpu_batch_set_cache": [vp, vp],
+        "fwgpu_batch_set_caches": [vp, vp, u32, vp],
         "fwgpu_dist_unique_id": [vp, u64],
         "fwgpu_dist_init": [vp, vp, i32, i32, P(vp)],
         "fwgpu_dist_free": [vp],

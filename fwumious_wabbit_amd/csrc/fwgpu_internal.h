@@ -357,6 +357,35 @@ struct MetricsLaunch {
     unsigned long long *hist = nullptr;    // [2 * 512] their histograms (NULL: none)
 };
 hipError_t launch_metrics(const MetricsLaunch &a, hipStream_t stream);
+
+// ---- candidates of many requests in one launch, a context cache per example (requests.hip; regressor.cpp run_batch_requests).  The argument block of
+// these two kernels is their own: KernelParams is not touched.
+struct RequestsParams {
+    const float *ffm_w;             // [2^ffm_bits + F*k]
+    const float *lr;                // {w, acc} pairs
+    const uint32_t *ffm_hash;       // the entry batch (CSR), as KernelParams holds it
+    const float *ffm_val;
+    const uint8_t *ffm_fld;
+    const uint32_t *ffm_off;        // [n+1]
+    const uint32_t *lr_hash;
+    const float *lr_val;
+    const uint32_t *lr_off;         // [n+1]
+    float *pred;                    // [n]
+    const float *const *cache_T;    // [2 * n_caches] every cache's d_T, then every cache's d_dcf
+    const uint32_t *cache_of;       // [n] the cache of each example
+    float *base;                    // [n_caches] base(S), written by requests_base_kernel at the head of the launch
+    uint32_t n, n_caches;
+    uint32_t F, k, R;
+    uint32_t slots;                 // LDS slices of R floats per wave: min(F, the batch's largest FFM entry count)
+    int32_t has_lr;
+};
+struct RequestsShape {
+    uint32_t slots = 0, threads = 0, chunks = 0;
+    size_t lds_bytes = 0;
+};
+// false: one wave's slices do not fit lds_limit bytes
+bool requests_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out);
+hipError_t launch_requests(const RequestsParams &p, const RequestsShape &shape, hipStream_t stream);
 // The window table of one stream of examples, on the device.  score() sizes it for the launch's last window (growing geometrically: a new
 // allocation, the old rows copied on the stream, the stream waited for once before the old one is freed) and enqueues the kernel; no other
 // call of it allocates.  fetch() waits for the stream.
@@ -423,6 +452,13 @@ struct fwgpu_batch {
     void *tr_dev = nullptr;  // device blob holding the DevTranslator arrays
     fwgpu::DevTranslator tr{};
     std::unique_ptr<fwgpu::HostBatch> host_copy;  // entry batches with an example of more than 4096 FFM features / LR entries: walked example by example (regressor.cpp)
+    // a cache per example (fwgpu_batch_set_caches): predict-only launches take the requests route (requests.hip)
+    std::vector<const fwgpu_block_cache *> req_caches;  // the set (empty: none attached)
+    void *req_dev = nullptr;                            // one allocation: the pointer table [2 * set], base [set], cache_of [n]
+    size_t req_dev_bytes = 0;
+    const float *const *req_T = nullptr;
+    float *req_base = nullptr;
+    uint32_t *req_of = nullptr;
 };
 
 struct fwgpu_regressor {

@@ -567,12 +567,79 @@ static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int up
     return FWGPU_OK;
 }
 
+// Why the requests kernels (requests.hip) do not serve this regressor / batch shape, or NULL.  Asked when a set is attached and again at every launch.
+static const char *requests_refusal(const fwgpu_regressor *r, const fwgpu_batch *b) {
+    const uint32_t k = r->cfg.ffm_k, F = r->cfg.ffm_num_fields;
+    if (r->packed()) return "a packed regressor keeps no device-side context cache";
+    if (r->nn.n_layers) return "models with a deep head are not served by the requests route (fwgpu_batch_set_cache serves them)";
+    if (b->records) return "a record batch is not served by the requests route (an entry batch of the filtered buffers is)";
+    if (b->host_copy) return "the batch holds an oversize example (more than 4096 entries of a kind, or beyond the fused kernel's LDS)";
+    if (k == 0) return "the model has no FFM block";
+    if (k % 4 != 0) return "ffm_k is no multiple of 4 (the requests kernel has no one-float-per-lane form)";
+    if (F > 256) return "more than 256 fields";
+    if (!b->aligned4) return "an FFM entry's row does not start on a 16-byte boundary (hash & 3 != 0)";
+    return nullptr;
+}
+
+// takes the set off the batch (hipFree waits for the launches that still read the table)
+static void requests_detach(fwgpu_batch *b) {
+    if (b->req_dev) (void)hipFree(b->req_dev);
+    b->req_dev = nullptr;
+    b->req_dev_bytes = 0;
+    b->req_T = nullptr;
+    b->req_base = nullptr;
+    b->req_of = nullptr;
+    b->req_caches.clear();
+}
+
+// predict-only launch of an entry batch with a cache per example: base(S) of every cache of the set, then one wavefront per candidate, on `stream`
+static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream) {
+    if (update) return fail(FWGPU_ERR_INVALID, "a batch with a cache per example (fwgpu_batch_set_caches) is predict-only: update must be 0");
+    if (const char *why = requests_refusal(r, b)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + why);
+    const uint32_t F = r->cfg.ffm_num_fields, k = r->cfg.ffm_k, R = F * k;
+    RequestsShape shape;
+    if (!requests_launch_shape(F, R, b->max_ffm, r->lds_per_cu, &shape))
+        return fail(FWGPU_ERR_RANGE, "requests route: min(fields, the batch's largest FFM entry count) * F * k floats of one candidate do not fit the 160 KiB LDS");
+    RequestsParams p{};
+    p.ffm_w = r->d_ffm_w;
+    p.lr = r->d_lr;
+    p.ffm_hash = b->ffm_hash;
+    p.ffm_val = b->ffm_val;
+    p.ffm_fld = b->ffm_fld;
+    p.ffm_off = b->ffm_off;
+    p.lr_hash = b->lr_hash;
+    p.lr_val = b->lr_val;
+    p.lr_off = b->lr_off;
+    p.pred = b->pred;
+    p.cache_T = b->req_T;
+    p.cache_of = b->req_of;
+    p.base = b->req_base;
+    p.n = b->n;
+    p.n_caches = (uint32_t)b->req_caches.size();
+    p.F = F;
+    p.k = k;
+    p.R = R;
+    p.slots = shape.slots;
+    p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
+    r->last_launch[0] = FWGPU_KERNEL_REQUESTS;
+    r->last_launch[1] = (int32_t)shape.chunks;
+    r->last_launch[2] = r->last_launch[3] = r->last_launch[4] = r->last_launch[5] = 0;
+    r->last_launch[6] = (int32_t)shape.threads;
+    r->last_launch[7] = (int32_t)shape.lds_bytes;
+    FWGPU_HIP(launch_requests(p, shape, stream));
+    return FWGPU_OK;
+}
+
 // (`route`: where fwgpu_learn_batch records the path the launch took -- fwgpu_debug_last_route; the single-example calls pass none)
 static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream, int32_t *route = nullptr) {
     if (route) *route = FWGPU_ROUTE_PACKED;
     if (r->packed()) return run_batch_packed(r, b, mode, update, stream);
     if (route) *route = FWGPU_ROUTE_NONE;
     if (b->n == 0) return FWGPU_OK;
+    if (!b->req_caches.empty()) {  // a cache per example (fwgpu_batch_set_caches): the requests kernels, in both modes
+        if (route) *route = FWGPU_ROUTE_REQUESTS;
+        return run_batch_requests(r, b, update, stream);
+    }
     if (route) *route = FWGPU_ROUTE_HOST_WALK;
     if (b->host_copy) return run_batch_by_example(r, b, update, stream);  // (an example beyond what the fused kernel stages: see learn_one_chunked)
     if (route) *route = FWGPU_ROUTE_FUSED;
@@ -1710,11 +1777,68 @@ int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *c) {
     if (c && b->records && !c->d_cover)
         return fail(FWGPU_ERR_INVALID, "a record batch needs a context cache that knows the context's record (fwgpu_block_cache_cover_record)");
     b->cache = c;
+    requests_detach(b);  // (one cache for the whole batch replaces a set, as a set replaces it)
+    return FWGPU_OK;
+}
+
+// A cache PER EXAMPLE: example i of the entry batch holds all LR entries of its request and the FFM entries
+// fwgpu_block_cache_filter(caches[cache_of_example[i]], ...) leaves.  Predict-only launches of the batch then take the requests route
+// (requests.hip: FWGPU_ROUTE_REQUESTS).  The pointer table and the index array are copied here; the caches are referenced and must
+// outlive the launches (a cache refilled by fwgpu_setup_cache on the same handle is read as refilled).  n_caches == 0 detaches.
+// A refused call leaves the batch as it was.
+int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches, const uint32_t *cache_of_example) {
+    if (!b) return fail(FWGPU_ERR_INVALID, "NULL batch");
+    if (n_caches == 0) {
+        requests_detach(b);
+        return FWGPU_OK;
+    }
+    if (!caches || (b->n && !cache_of_example)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (!b->owner) return fail(FWGPU_ERR_INVALID, "set_caches: the batch has no regressor");
+    if (const char *why = requests_refusal(b->owner, b)) return fail(FWGPU_ERR_INVALID, std::string("set_caches: ") + why);
+    for (uint32_t c = 0; c < n_caches; c++) {
+        if (!caches[c]) return fail(FWGPU_ERR_INVALID, "set_caches: NULL cache");
+        if (caches[c]->owner != b->owner) return fail(FWGPU_ERR_INVALID, "set_caches: a cache belongs to another regressor");
+    }
+    for (uint32_t i = 0; i < b->n; i++)
+        if (cache_of_example[i] >= n_caches) return fail(FWGPU_ERR_INVALID, "set_caches: cache_of_example holds an index >= n_caches");
+    // one allocation: d_T of every cache, d_dcf of every cache, base [n_caches] (8-byte slots), then cache_of [n]
+    const size_t table = 2 * (size_t)n_caches * sizeof(float *), base = (((size_t)n_caches * sizeof(float)) + 7) & ~(size_t)7;
+    std::vector<unsigned char> host(table + base + (size_t)b->n * sizeof(uint32_t), 0);
+    const float **tp = reinterpret_cast<const float **>(host.data());
+    for (uint32_t c = 0; c < n_caches; c++) {
+        tp[c] = caches[c]->d_T;
+        tp[n_caches + c] = caches[c]->d_dcf;
+    }
+    if (b->n) memcpy(host.data() + table + base, cache_of_example, (size_t)b->n * sizeof(uint32_t));
+    FWGPU_HIP(hipSetDevice(b->owner->device));
+    // (a set that fits the allocation of the one it replaces is written over it: the call must not overlap a launch of this batch that is still in
+    // flight, as with every other change of a batch's contents)
+    void *dev = b->req_dev_bytes >= host.size() ? b->req_dev : nullptr;
+    const bool fresh = dev == nullptr;
+    if (fresh && hipMalloc(&dev, host.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FWGPU_ERR_OOM, "set_caches: no device memory for the cache table");
+    }
+    if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        if (fresh) (void)hipFree(dev);
+        return fail(FWGPU_ERR_DEVICE, "set_caches: copy to the device failed");
+    }
+    if (fresh) {
+        requests_detach(b);
+        b->req_dev_bytes = host.size();
+    }
+    b->cache = nullptr;
+    b->req_dev = dev;
+    b->req_T = reinterpret_cast<const float *const *>(dev);
+    b->req_base = reinterpret_cast<float *>(static_cast<unsigned char *>(dev) + table);
+    b->req_of = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(dev) + table + base);
+    b->req_caches.assign(caches, caches + n_caches);
     return FWGPU_OK;
 }
 
 int fwgpu_batch_free(fwgpu_batch *b) {
     if (!b) return FWGPU_OK;
+    requests_detach(b);
     if (b->dev) (void)hipFree(b->dev);
     if (b->tr_dev) (void)hipFree(b->tr_dev);
     if (b->host_block) (void)hipHostFree(b->host_block);

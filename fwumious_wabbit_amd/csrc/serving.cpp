@@ -22,6 +22,7 @@
 // line's record breaks the record rule or cannot be split off the context, a predictor without a device cache (packed weights, FFM-less models,
 // no fw_setup_cache yet) or with a context that is not its own record, and FWGPU_SERVING_HOST_PARSE=1 take fwgpu_predictor_predict_batch on
 // the split lines instead (fwgpu_predictor_last_text_route: fell_back).  FWGPU_SERVING_TEXT_PIECE=<bytes>: text per parser pass.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,8 +49,10 @@ struct SharedModel {  // what clone_lite shares: the immutable regressor and the
     fwgpu_batch *batch = nullptr;  // device buffers of fwgpu_predictor_predict_batch, grown on demand and reused
     fwgpu_batch *one = nullptr;    // single requests: a host-mapped batch (no copy calls, no memset: launch + one synchronisation)
     fwgpu_text_parser *tp = nullptr;  // fwgpu_predictor_predict_text: the device parser, made by the first call, used under mu
+    fwgpu_batch *requests = nullptr;  // fwgpu_predictor_predict_requests: its entry batch, grown on demand and reused (n_cap examples)
     ~SharedModel() {
         if (tp) fwgpu_text_parser_free(tp);
+        if (requests) fwgpu_batch_free(requests);
         if (batch) fwgpu_batch_free(batch);
         if (one) fwgpu_batch_free(one);
         if (re) fwgpu_free(re);
@@ -634,6 +637,163 @@ int fwgpu_predictor_predict_text(FfiPredictor *ptr, const char *text, uint64_t l
     b->delta_records = false;
     if (rc != FWGPU_OK) return rc;
     for (size_t j = 0; j < slot.size(); j++) out[slot[j]] = preds[j];
+    return FWGPU_OK;
+}
+
+// The candidates of SEVERAL requests in one launch: predictors[r] (the prototype and clone_lite copies of one model, each after its own
+// fw_setup_cache; the same one may appear twice) with its lines inputs[r][0 .. n_inputs[r]).  The existing entry route per line -- parse after the
+// context's prefix, translate, filter by the cache's features -- with the requests spread over the worker pool, then ONE shared entry batch with a cache
+// per example (fwgpu_batch_set_caches) and ONE launch, under the model's mutex taken once.
+int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs, const uint32_t *n_inputs,
+                                     float *const *out) {
+    if (n_requests == 0) return FWGPU_OK;
+    if (!predictors || !inputs || !n_inputs || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    static const char *kSee = " (fwgpu_predictor_predict_batch serves this predictor, one request per call)";
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < n_requests; r++) {
+        if (!predictors[r] || (n_inputs[r] && (!inputs[r] || !out[r]))) return fail(FWGPU_ERR_INVALID, "NULL argument");
+        if (predictors[r]->model != predictors[0]->model)
+            return fail(FWGPU_ERR_INVALID, std::string("predict_requests: the predictors are not the prototype and clone_lite copies of ONE model") + kSee);
+        total += n_inputs[r];
+    }
+    if (total > 0xffffffffull) return fail(FWGPU_ERR_RANGE, "predict_requests: more than 2^32 - 1 lines");
+    SharedModel &m = *predictors[0]->model;
+    if (m.re->packed()) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a --packed_weights predictor keeps no device cache") + kSee);
+    if (m.re->cfg.ffm_k == 0) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a model without an FFM block keeps no device cache") + kSee);
+    if (m.re->nn.n_layers) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
+    std::vector<const fwgpu_block_cache *> caches;  // the set: every predictor's cache once
+    std::vector<uint32_t> cache_of_request(n_requests);
+    for (uint32_t r = 0; r < n_requests; r++) {
+        const FfiPredictor *p = predictors[r];
+        if (!p->cache || !p->prefix) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a predictor has no device cache (no fw_setup_cache yet)") + kSee);
+        size_t c = 0;
+        while (c < caches.size() && caches[c] != p->cache) c++;
+        if (c == caches.size()) caches.push_back(p->cache);
+        cache_of_request[r] = (uint32_t)c;
+        for (uint32_t j = 0; j < n_inputs[r]; j++) out[r][j] = kExceptionErrorCode;
+    }
+    if (total == 0) return FWGPU_OK;
+    // the lines of all requests in equal shares per thread (FWGPU_SERVING_THREADS overrides; by default one thread per 128 lines, up to the cores there are and at most 32)
+    FfiPredictor *host = predictors[0];  // its worker pool and per-thread parsers serve the call
+    unsigned T = 1;
+    {
+        const char *env = std::getenv("FWGPU_SERVING_THREADS");
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        T = env && std::atoi(env) > 0 ? (unsigned)std::atoi(env) : std::min<unsigned>(std::min<unsigned>(32, hw), std::max<unsigned>(1, (unsigned)(total / 128)));
+        T = std::min<unsigned>(T, 64);
+    }
+    while (host->parts.size() < T) host->parts.push_back(std::make_unique<Part>());
+    std::vector<uint64_t> first(n_requests + 1, 0);  // the lines of all requests, numbered through: thread t takes an equal share of them
+    for (uint32_t r = 0; r < n_requests; r++) first[r + 1] = first[r] + n_inputs[r];
+    std::vector<std::vector<uint32_t>> where(T), line(T), which(T);  // per thread and kept example: its request, its line there, its cache of the set
+    auto work = [&](unsigned t) {
+        Part &pt = *host->parts[t];
+        pt.reset();
+        if (!pt.parser && fwgpu_parser_create(m.vw, &pt.parser) != FWGPU_OK) {
+            pt.hb_ok = false;
+            return;
+        }
+        std::vector<uint32_t> &rec = pt.rec;
+        if (rec.size() < 4096) rec.resize(4096);
+        std::vector<fwgpu_lr_entry> t_lr;
+        std::vector<fwgpu_ffm_entry> t_ffm;
+        const uint64_t a = total * t / T, e = total * (t + 1) / T;
+        uint32_t r = (uint32_t)(std::upper_bound(first.begin(), first.end(), a) - first.begin()) - 1;
+        for (uint64_t g = a; g < e; g++) {
+            while (g >= first[r + 1]) r++;
+            const uint32_t j = (uint32_t)(g - first[r]);
+            const FfiPredictor *p = predictors[r];
+            const char *text = inputs[r][j];
+            if (!text) continue;
+            uint32_t nw = 0;
+            int rc;
+            for (;;) {
+                rc = fwgpu_parser_parse_after_prefix(pt.parser, p->prefix, text, std::strlen(text), rec.data(), (uint32_t)rec.size(), &nw);
+                if (rc == FWGPU_ERR_RANGE && rec.size() < (1u << 24)) {
+                    rec.resize(rec.size() * 4);
+                    continue;
+                }
+                break;
+            }
+            if (rc != FWGPU_OK || nw == 0) {
+                if (rc == FWGPU_OK) out[r][j] = kEofErrorCode;
+                continue;
+            }
+            rec[1] = 0;  // a request carries no label
+            float label, imp;
+            if (translate_record(&m.tr, rec.data(), nw, t_lr, t_ffm, &label, &imp) != FWGPU_OK) continue;
+            uint32_t kept = 0;
+            if (fwgpu_block_cache_filter(p->cache, t_ffm.data(), (uint32_t)t_ffm.size(), t_ffm.data(), &kept) != FWGPU_OK) continue;
+            if (append_example(m.re, pt.hb, t_lr.data(), (uint32_t)t_lr.size(), t_ffm.data(), kept, 0.0f, 1.0f) != FWGPU_OK) {
+                pt.hb_ok = false;
+                continue;
+            }
+            where[t].push_back(r);
+            line[t].push_back(j);
+            which[t].push_back(cache_of_request[r]);
+        }
+    };
+    host->workers.run(T, work);
+    // one entry batch: every thread's SoA arrays go to the device from where the thread left them, at their offsets (no merged host copy); only the
+    // example offsets are rebased here
+    std::vector<size_t> fb(T + 1, 0), lb(T + 1, 0);
+    std::vector<uint32_t> ffm_off(1, 0), lr_off(1, 0), ex_req, ex_line, ex_cache;
+    uint32_t max_lr = 0, max_ffm = 0;
+    bool aligned4 = true;
+    for (unsigned t = 0; t < T; t++) {
+        const HostBatch &src = host->parts[t]->hb;
+        if (!host->parts[t]->hb_ok) return fail(FWGPU_ERR_RANGE, "predict_requests: a candidate's entries were refused (see append_example)");
+        fb[t + 1] = fb[t] + src.ffm_hash.size();
+        lb[t + 1] = lb[t] + src.lr_hash.size();
+        for (size_t j = 1; j < src.ffm_off.size(); j++) ffm_off.push_back(src.ffm_off[j] + (uint32_t)fb[t]);
+        for (size_t j = 1; j < src.lr_off.size(); j++) lr_off.push_back(src.lr_off[j] + (uint32_t)lb[t]);
+        max_lr = std::max(max_lr, src.max_lr);
+        max_ffm = std::max(max_ffm, src.max_ffm);
+        aligned4 = aligned4 && src.aligned4;
+        ex_req.insert(ex_req.end(), where[t].begin(), where[t].end());
+        ex_line.insert(ex_line.end(), line[t].begin(), line[t].end());
+        ex_cache.insert(ex_cache.end(), which[t].begin(), which[t].end());
+    }
+    const uint32_t nrec = (uint32_t)ex_req.size();
+    if (nrec == 0) return FWGPU_OK;
+    if (fb[T] > 0xffffffffull || lb[T] > 0xffffffffull) return fail(FWGPU_ERR_RANGE, "predict_requests: more than 2^32 - 1 entries in one call");
+    if (max_ffm > 4096 || max_lr > 4096)
+        return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a line has more than 4096 entries of a kind") + kSee);
+    std::lock_guard<std::mutex> g(m.mu);
+    int rc = FWGPU_OK;
+    if (!m.requests || m.requests->n_cap < nrec || m.requests->n_lr < lb[T] || m.requests->n_ffm < fb[T]) {
+        if (m.requests) fwgpu_batch_free(m.requests);
+        m.requests = nullptr;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2ull * nrec, 256), 0xffffffffull);
+        if ((rc = batch_alloc(m.re, cap, std::max<uint64_t>(2 * lb[T], 1 << 16), std::max<uint64_t>(2 * fb[T], 1 << 14), &m.requests)) != FWGPU_OK) return rc;
+        m.requests->n_cap = cap;
+    }
+    fwgpu_batch *eb = m.requests;
+    eb->n = nrec;
+    auto up = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == FWGPU_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            rc = fail(FWGPU_ERR_DEVICE, "predict_requests: copy to the device failed");
+    };
+    for (unsigned t = 0; t < T; t++) {  // (labels, importances and combo slots are not read by a predict-only launch of a model without a deep head)
+        const HostBatch &src = host->parts[t]->hb;
+        up(eb->ffm_hash + fb[t], src.ffm_hash.data(), src.ffm_hash.size() * 4);
+        up(eb->ffm_val + fb[t], src.ffm_val.data(), src.ffm_val.size() * 4);
+        up(eb->ffm_fld + fb[t], src.ffm_fld.data(), src.ffm_fld.size());
+        up(eb->lr_hash + lb[t], src.lr_hash.data(), src.lr_hash.size() * 4);
+        up(eb->lr_val + lb[t], src.lr_val.data(), src.lr_val.size() * 4);
+    }
+    up(eb->ffm_off, ffm_off.data(), ffm_off.size() * 4);
+    up(eb->lr_off, lr_off.data(), lr_off.size() * 4);
+    eb->max_lr = max_lr;
+    eb->max_ffm = max_ffm;
+    eb->aligned4 = aligned4;
+    if (rc == FWGPU_OK) rc = fwgpu_batch_set_caches(eb, caches.data(), (uint32_t)caches.size(), ex_cache.data());
+    if (rc == FWGPU_OK) rc = fwgpu_learn_batch(m.re, eb, FWGPU_MODE_HOGWILD, /*update=*/0, nullptr);
+    std::vector<float> preds(nrec);
+    if (rc == FWGPU_OK) rc = fwgpu_batch_predictions(eb, preds.data(), nrec, nullptr);
+    // (the set stays attached to this private batch until the next call replaces it: no launch happens in between, and detaching would free its table)
+    if (rc != FWGPU_OK) return rc;
+    for (uint32_t i = 0; i < nrec; i++) out[ex_req[i]][ex_line[i]] = preds[i];
     return FWGPU_OK;
 }
 

@@ -169,6 +169,16 @@ class Batch:
         """predict-only launches of this entry batch start every example from the context cache (None detaches it)"""
         check(capi.lib().fwgpu_batch_set_cache(self.h, cache.h if cache is not None else None))
 
+    def set_caches(self, caches, cache_of_example):
+        """a context cache PER EXAMPLE (candidates of many requests in one launch): example i of this entry batch holds all LR entries of its request
+        and the FFM entries caches[cache_of_example[i]].filter() leaves; predict-only launches then take ROUTE_REQUESTS.  An empty list detaches
+        (fwgpu_batch_set_caches)."""
+        handles = (C.c_void_p * max(len(caches), 1))(*[c.h for c in caches])
+        idx = np.ascontiguousarray(cache_of_example, dtype=np.uint32)
+        if len(caches) and len(idx) != self.n:
+            raise ValueError("cache_of_example: one index per example of the batch")
+        check(capi.lib().fwgpu_batch_set_caches(self.h, handles, len(caches), ptr(idx)))
+
     def predictions(self, stream=None):
         out = np.zeros(self.n, dtype=np.float32)
         check(capi.lib().fwgpu_batch_predictions(self.h, ptr(out), self.n, stream))

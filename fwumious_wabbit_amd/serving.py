@@ -25,8 +25,29 @@ def _lib():
         L.fwgpu_predictor_predict_text.restype = C.c_int
         L.fwgpu_predictor_last_text_route.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.fwgpu_predictor_last_text_route.restype = C.c_int
+        L.fwgpu_predictor_predict_requests.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_uint32),
+                                                       C.POINTER(C.c_void_p)]
+        L.fwgpu_predictor_predict_requests.restype = C.c_int
         L._fw_ffi_ready = True
     return L
+
+
+def predict_requests(predictors, requests):
+    """The candidates of several requests in ONE launch (fwgpu_predictor_predict_requests): predictors[r] -- the prototype and clone_lite copies of one
+    model, each after its own setup_cache -- scores requests[r], a list of str or the array Predictor.encode_batch made of one.  Returns one float32
+    array per request: what predict_with_cache returns per line, -1.0 for a line that does not parse."""
+    if len(predictors) != len(requests):
+        raise ValueError("one list of lines per predictor")
+    L = _lib()
+    n = len(predictors)
+    arrs = [t if isinstance(t, C.Array) else Predictor.encode_batch(t) for t in requests]
+    outs = [np.zeros(len(a), dtype=np.float32) for a in arrs]
+    handles = (C.c_void_p * max(n, 1))(*[p.p for p in predictors])
+    inputs = (C.POINTER(C.c_char_p) * max(n, 1))(*[C.cast(a, C.POINTER(C.c_char_p)) for a in arrs])
+    counts = (C.c_uint32 * max(n, 1))(*[len(a) for a in arrs])
+    out_ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data if o.size else None for o in outs])
+    capi.check(L.fwgpu_predictor_predict_requests(handles, n, inputs, counts, out_ptrs))
+    return outs
 
 
 class Predictor:

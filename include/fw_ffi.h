@@ -46,6 +46,17 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
 int fwgpu_predictor_predict_text(FfiPredictor *p, const char *text, uint64_t len, int with_cache, float *out, uint64_t cap, uint64_t *n);
 int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint64_t *host_lines, int *fell_back);
 
+/* The candidates of SEVERAL requests in ONE device launch.  predictors[r] are the prototype and clone_lite copies of one model, each
+ * after its own fw_setup_cache (the same predictor may appear twice); inputs[r][j], j < n_inputs[r], is what
+ * fw_predict_with_cache(predictors[r], .) would be given, out[r][j] what it would return, -1.0 for a line that does not parse or
+ * gives no record.  Every line is parsed behind its predictor's context, translated and filtered by that predictor's cache on the
+ * host's worker threads; one entry batch with a cache per example follows (fwgpu_batch_set_caches), whose kernel's work per candidate
+ * follows the candidate's own features.  FWGPU_ERR_INVALID, pointing to fwgpu_predictor_predict_batch: predictors of different
+ * models, a predictor without a device cache (no fw_setup_cache yet, --packed_weights, a model without an FFM block), a model with
+ * a deep head.  Concurrent callers are not coalesced: each call is one launch under the model's mutex. */
+int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs,
+                                     const uint32_t *n_inputs, float *const *out);
+
 #ifdef __cplusplus
 }
 #endif

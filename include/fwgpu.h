@@ -222,6 +222,19 @@ int fwgpu_learn_batch_sync(fwgpu_regressor *r, fwgpu_batch *b, fwgpu_split *sp, 
 /* predict-only launches of this batch start every example's field sums from this context cache (NULL detaches it); a record
  * batch needs a cache that went through fwgpu_block_cache_cover_record */
 int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *cache);
+/* A context cache PER EXAMPLE: candidates of many requests in one launch.  `b` is an entry batch whose example i holds all LR entries
+ * of its request and the FFM entries fwgpu_block_cache_filter(caches[cache_of_example[i]], ...) leaves (what an entry batch with
+ * fwgpu_batch_set_cache holds, per request).  fwgpu_learn_batch(r, b, mode, update = 0, stream) then takes FWGPU_ROUTE_REQUESTS in
+ * both modes (a predict-only launch has no order): the work per candidate follows the candidate's own features, not F * F * k.
+ * update != 0 on such a batch is FWGPU_ERR_INVALID.  The pointer table and the index array are copied at the call; the caches are
+ * referenced and must outlive the launches -- a cache refilled by fwgpu_setup_cache on the same handle is read as refilled, by the
+ * next launch.  Like every change of a batch's contents, the call must not overlap a launch of the batch that is still in flight.
+ * n_caches == 0 detaches; fwgpu_batch_set_cache on the same batch replaces the set, and the other way round.
+ * FWGPU_ERR_INVALID, the batch left as it was: a record batch, an index >= n_caches, a cache of another regressor, a regressor with
+ * a deep head or packed weights, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
+ * whose min(fields, largest FFM entry count of an example) * F * k floats exceed the 160 KiB LDS returns FWGPU_ERR_RANGE. */
+int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches,
+                           const uint32_t *cache_of_example /* [examples of b] */);
 /* Enqueue one pass over the batch on `stream`: for every example, Regressor::learn(fb, update)
  * (update=0: Regressor::predict).  Predictions land in the batch's device buffer. Asynchronous. */
 int fwgpu_learn_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, void *stream);
@@ -571,6 +584,7 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value);
 #define FWGPU_ROUTE_HEAD_BATCHED_REFUSED 3 /* ... which refused the batch's shape (FWGPU_ERR_RANGE); the batch was re-run on the fused example kernel, per example */
 #define FWGPU_ROUTE_PACKED 4               /* packed regressor: the packed predict kernel (or its refusal) */
 #define FWGPU_ROUTE_HOST_WALK 5            /* a batch with an oversize example: walked example by example from its host copy */
+#define FWGPU_ROUTE_REQUESTS 6             /* predict-only entry batch with a cache per example (fwgpu_batch_set_caches) */
 int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 /* What the regressor's last example-kernel launch ran, from its RESOLVED launch parameters (host side, read-only; every batch launch that reaches the
  * example kernel records it, the launch of a refused batch does not): the first n <= FWGPU_LAUNCH_INFO_LEN of
@@ -584,6 +598,7 @@ int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 #define FWGPU_KERNEL_VEC4 1     /* generic kernel, 16 bytes per lane */
 #define FWGPU_KERNEL_RESIDENT 2 /* register-resident kernel (rows of up to 256 floats, or up to 512 where 256 % k == 0) */
 #define FWGPU_KERNEL_PACKED 3   /* ... its predict-only instantiation on a packed table */
+#define FWGPU_KERNEL_REQUESTS 4 /* the requests kernels (FWGPU_ROUTE_REQUESTS): [1] = ceil(R / 256), [6] = threads per workgroup, [7] = LDS bytes, [2]..[5] = 0 */
 #define FWGPU_LAUNCH_INFO_LEN 8
 int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
