@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("FWGPU_LIBRARY") or os.path.join(_HERE, "lib", "libfwg
 OK = 0
 ERR_INVALID = 1
 ERR_RANGE = 4
+ERR_FORMAT = 5
 ERR_PARSE, ERR_IO, PARSE_FLUSH, PARSE_HOGWILD_LOAD = 6, 7, 100, 101
 FFM_F32, FFM_F16_BUCKETS = 0, 1  # fwgpu_ffm_storage
 OPT_SGD, OPT_ADAGRAD_FLEX, OPT_ADAGRAD_LUT = 100, 200, 300
@@ -259,6 +260,17 @@ def lib():
         "fwgpu_pack_regressor": [vp, P(vp)],
         "fwgpu_debug_quantize": [i32, vp, u64, vp, u64, P(i32)],
         "fwgpu_debug_quantize_rates": [vp, vp],
+        "fwgpu_diff_bytes": [vp, vp, u64, u64, u64, vp, u64, P(u64), P(u64)],
+        "fwgpu_diff_apply_bytes": [vp, u64, u64, vp, u64, P(u64)],
+        "fwgpu_image_capture": [vp, vp, vp, i32, P(vp)],
+        "fwgpu_image_load": [C.c_char_p, i32, P(vp)],
+        "fwgpu_image_len": [vp, P(u64), P(u64)],
+        "fwgpu_image_read": [vp, vp, u64],
+        "fwgpu_image_diff": [vp, vp, vp, u64, P(u64), P(u64)],
+        "fwgpu_packed_apply_diff": [vp, vp, u64, P(u64)],
+        "fwgpu_debug_diff": [i32, vp, vp, u64, u64, u64, vp, u64, P(u64), P(u64)],
+        "fwgpu_debug_diff_geometry": [P(u32)],
+        "fwgpu_debug_diff_rates": [vp, vp, vp],
         "fwgpu_set_wiring": [vp, i32],
         "fwgpu_model_convert_inference": [C.c_char_p, C.c_char_p, i32],
         "fwgpu_quantize_ffm_weights": [vp, u64, vp, u64],
@@ -282,7 +294,7 @@ def lib():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = i32
-    for name in ("fwgpu_vwmap_free", "fwgpu_parser_free", "fwgpu_text_parser_free", "fwgpu_parse_prefix_free", "fwgpu_cache_free", "fwgpu_mi_free", "fwgpu_input_close"):
+    for name in ("fwgpu_vwmap_free", "fwgpu_parser_free", "fwgpu_text_parser_free", "fwgpu_parse_prefix_free", "fwgpu_cache_free", "fwgpu_mi_free", "fwgpu_input_close", "fwgpu_image_free"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = None
     for name in ("fwgpu_vwmap_num_namespaces", "fwgpu_vwmap_num_entries"):

@@ -338,6 +338,46 @@ hipError_t launch_quant_buckets(const float *w, uint64_t n, float increment, flo
 hipError_t launch_lr_weights(const float *pairs, uint64_t n_entries, float *w, hipStream_t stream);                // {w, acc} pairs -> w
 hipError_t launch_lr_weights_pairs(const float *pairs, uint64_t n_entries, float *dst_pairs, hipStream_t stream);  // {w, acc} pairs -> {w, 0} pairs
 
+// ---- the byte diff of two inference weights sections and the hot patch of a packed regressor (patch.hip; the stream: diff_stream.h)
+constexpr uint32_t kDiffThreads = 256;                    // four waves; a wave owns a contiguous quarter of its workgroup's tile
+constexpr uint32_t kDiffLaneBytes = 16;                   // one 16-byte load of each input per lane and step
+constexpr uint32_t kDiffSteps = 4;                        // steps of 64 lanes x 16 bytes a wave walks
+constexpr uint32_t kDiffWaveBytes = 64 * kDiffLaneBytes * kDiffSteps;
+constexpr uint32_t kDiffTileBytes = kDiffWaveBytes * (kDiffThreads / 64);  // 16 KiB: 2^18 tiles for a 4 GiB section
+constexpr uint32_t kDiffScanThreads = 1024;               // the tile scan: one workgroup, a contiguous run of tiles per lane
+struct DiffTile {   // size pass -> scan: one tile's entries, positions relative to the tile's first byte
+    uint32_t count;  // differing bytes
+    uint32_t first, last;
+    uint32_t rest;   // encoded size of all entries but the first (whose delta reaches into earlier tiles)
+};
+struct DiffTileStart {  // scan -> emit pass
+    unsigned long long prev;  // index of the last entry before the tile: of the nearest earlier tile that has one, else the carried-in prev_index
+    unsigned long long out;   // where the tile's entries begin in the stream
+};
+struct DiffArgs {
+    const uint8_t *a, *b;            // two device arrays of n bytes, 16-byte aligned; nothing beyond n is read
+    unsigned long long n;
+    unsigned long long base_offset;  // an entry's index is base_offset + i
+    unsigned long long prev_index;   // the last entry before this range (<= base_offset)
+    unsigned long long n_tiles;
+    DiffTile *tiles;                 // [n_tiles]
+    DiffTileStart *starts;           // [n_tiles]
+    unsigned long long *totals;      // {stream bytes, entries}
+    uint8_t *out;                    // emit pass: the stream, totals[0] bytes, 16-byte aligned
+};
+hipError_t launch_diff_size(const DiffArgs &d, hipStream_t stream);
+hipError_t launch_diff_scan(const DiffArgs &d, hipStream_t stream);
+hipError_t launch_diff_emit(const DiffArgs &d, hipStream_t stream);
+struct PatchArgs {  // the scatter of a stream's entries into a packed regressor's tables
+    const unsigned long long *index;  // [n] offsets into the file's weights section, ascending
+    const uint8_t *to;                // [n]
+    unsigned long long n;
+    unsigned long long lr_bytes;      // the section's LR part: byte j -> byte (j / 4) * 8 + j % 4 of `lr`
+    unsigned long long q_at, q_bytes; // the buckets begin at q_at: byte j -> byte j - q_at of `q`
+    uint8_t *lr, *q;
+};
+hipError_t launch_patch_scatter(const PatchArgs &p, hipStream_t stream);
+
 // ---- progressive / hold-out loss (metrics.hip): one launch scores n predictions against their labels into a window table and two totals
 constexpr uint64_t kMetricsNoLabel = 255;  // parser.rs:28 NO_LABEL, as translate_record turns it into a float
 struct MetricsLaunch {
@@ -474,6 +514,9 @@ struct fwgpu_regressor {
     uint64_t ffm_q_bytes = 0;           // bytes of that allocation
     float q_increment = 0, q_min = 0;   // the file's 8-byte header: w = q_min + f32(bucket) * q_increment
     bool packed() const { return d_ffm_q != nullptr; }
+    // where the packed tables came from (fwgpu_packed_apply_diff): a quantised inference file's own bytes can be patched from a diff of two such files
+    uint64_t file_header_bytes = 0;     // that file's bytes before its weights section; 0: no such file (fwgpu_pack_regressor, or quantised at load)
+    bool file_quantized_at_load = false;
     int placement_tries = 0;                     // candidate allocations timed for d_ffm_acc (regressor.cpp: place_ffm_acc)
     float placement_ms_lo = 0, placement_ms_hi = 0;  // fastest / slowest pair probe among them
     float placement_ms_single = 0;                    // the same probe on the weight table alone
@@ -498,6 +541,14 @@ struct fwgpu_regressor {
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     void *metrics_scratch = nullptr;  // fwgpu_batch_metrics: one set of sums and histograms on the device (metrics.hip)
+};
+
+// The inference file fwgpu_model_save_inference would write, split in two (model_file.cpp: capture and load; patch.hip: the diff)
+struct fwgpu_image {
+    int device = 0;
+    std::vector<uint8_t> header;  // host: write_header + the u64 element count
+    uint8_t *d_weights = nullptr; // device, ONE allocation in file order: LR weights (f32), the FFM block, the dense layers' weights
+    uint64_t weights_bytes = 0;
 };
 
 // device buffers of one synchronous micro-batch (regressor.cpp "split pipeline")

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -707,6 +708,153 @@ int fwgpu_model_save_inference(const char *path, const fwgpu_vwmap *vw, const fw
     return FWGPU_OK;
 }
 
+// ---- the same file as an image: header on the host, weights section in one device allocation (include/fwgpu.h)
+static int image_alloc(fwgpu_image *img) {
+    if (hipMalloc((void **)&img->d_weights, img->weights_bytes ? img->weights_bytes : 16) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FWGPU_ERR_OOM, "image: no device memory for the weights section (" + std::to_string(img->weights_bytes) + " bytes)");
+    }
+    return FWGPU_OK;
+}
+
+void fwgpu_image_free(fwgpu_image *img) {
+    if (!img) return;
+    (void)hipSetDevice(img->device);
+    (void)hipFree(img->d_weights);
+    delete img;
+}
+
+int fwgpu_image_capture(fwgpu_regressor *r, const fwgpu_vwmap *vw, const fwgpu_model_instance *mi, int quantize_weights, fwgpu_image **out) {
+    if (!r || !vw || !mi || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    int rc = refuse_packed(r, "image_capture");
+    if (rc) return rc;
+    BlobShape s;
+    rc = shape_from_mi(mi, &s);
+    if (rc) return rc;
+    uint64_t need = 0;
+    rc = fwgpu_serialized_len(r, &need);
+    if (rc) return rc;
+    if (mi->optimizer != r->cfg.optimizer || need != 8 + blob_body_bytes(r->cfg.optimizer, false, s))
+        return fail(FWGPU_ERR_INVALID, "image_capture: the regressor was not built from this ModelInstance");
+    std::unique_ptr<fwgpu_image, void (*)(fwgpu_image *)> img(new fwgpu_image(), fwgpu_image_free);
+    img->device = r->device;
+    try {  // the header, by the statements fwgpu_model_save_inference runs, into memory
+        fwgpu_model_instance inf = *mi;
+        fwgpu_mi_set_inference(&inf, quantize_weights);
+        char *mem = nullptr;
+        size_t mem_len = 0;
+        struct FreeMem {  // (declared before the stream: freed after the stream is closed)
+            char **p;
+            ~FreeMem() { free(*p); }
+        } free_mem{&mem};
+        File out_mem;
+        out_mem.f = open_memstream(&mem, &mem_len);
+        if (!out_mem.f) return fail(FWGPU_ERR_OOM, "image_capture: no memory stream for the header");
+        write_header(out_mem, vw, &inf);
+        out_mem.put_u64(s.elems());
+        std::fclose(out_mem.f);  // (fixes mem and mem_len)
+        out_mem.f = nullptr;
+        img->header.assign(reinterpret_cast<uint8_t *>(mem), reinterpret_cast<uint8_t *>(mem) + mem_len);
+    } catch (const std::exception &e) {
+        return fail(FWGPU_ERR_IO, e.what());
+    }
+    const bool quantized = quantize_weights && s.ffm_len;
+    const uint64_t lr_bytes = s.lr_len * 4, ffm_bytes = s.ffm_len ? (quantized ? 8 + 2 * s.ffm_len : 4 * s.ffm_len) : 0;
+    img->weights_bytes = lr_bytes + ffm_bytes + r->nn_len * 4;
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());  // the regressor's outstanding launches, as fwgpu_write_weights waits for them
+    if ((rc = image_alloc(img.get()))) return rc;
+    uint8_t *d = img->d_weights;
+    FWGPU_HIP(launch_lr_weights(r->d_lr, r->lr_len, reinterpret_cast<float *>(d), 0));
+    d += lr_bytes;
+    if (quantized) {
+        float inc = 0, mn = 0;
+        bool done = false;
+        // table to image on the device; a table the contract sends to the host route (quantize.hip) takes it here too
+        rc = quantize_on_device(r->device, r->d_ffm_w, s.ffm_len, reinterpret_cast<uint16_t *>(d + 8), &inc, &mn, &done);
+        if (rc) return rc;
+        if (done) {
+            uint8_t h[8];
+            std::memcpy(h, &inc, 4);
+            std::memcpy(h + 4, &mn, 4);
+            FWGPU_HIP(hipMemcpy(d, h, 8, hipMemcpyHostToDevice));  // (the block's header was formed on the host: quantize.hip)
+        } else {
+            std::vector<uint8_t> block;
+            if ((rc = ffm_quantized_block(r, block))) return rc;
+            FWGPU_HIP(hipMemcpy(d, block.data(), block.size(), hipMemcpyHostToDevice));
+        }
+    } else if (s.ffm_len) {
+        FWGPU_HIP(hipMemcpyAsync(d, r->d_ffm_w, ffm_bytes, hipMemcpyDeviceToDevice, 0));
+    }
+    d += ffm_bytes;
+    for (uint32_t l = 0; r->nn.n_layers && l <= r->nn.n_layers; l++) {  // block order, as nn_weights_read walks them
+        const size_t len = ((size_t)r->nn.in[l] + 1) * r->nn.out[l];
+        FWGPU_HIP(hipMemcpyAsync(d, r->d_nn_w + r->nn.off[l], len * 4, hipMemcpyDeviceToDevice, 0));
+        d += len * 4;
+    }
+    FWGPU_HIP(hipDeviceSynchronize());
+    if ((uint64_t)(d - img->d_weights) != img->weights_bytes) return fail(FWGPU_ERR_INVALID, "image_capture: the layers' sizes differ from the ModelInstance's");
+    *out = img.release();
+    return FWGPU_OK;
+}
+
+int fwgpu_image_load(const char *path, int device, fwgpu_image **out) {
+    if (!path || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    try {
+        File in;
+        in.f = std::fopen(path, "rb");
+        if (!in.f) return fail(FWGPU_ERR_IO, std::string("cannot open ") + path);
+        std::unique_ptr<fwgpu_vwmap, void (*)(fwgpu_vwmap *)> vw(nullptr, fwgpu_vwmap_free);
+        std::unique_ptr<fwgpu_model_instance> mi;
+        read_header(in, vw, mi);
+        BlobShape s;
+        int rc = shape_from_mi(mi.get(), &s);
+        if (rc) return rc;
+        const uint64_t count = in.u64();
+        if (count != s.elems())
+            return fail(FWGPU_ERR_FORMAT, "Lenghts of weights array in regressor file differ: got " + std::to_string(count) +
+                                              ", expected " + std::to_string(s.elems()));
+        if (mi->optimizer != FWGPU_OPT_SGD) return fail(FWGPU_ERR_INVALID, "image_load: not an inference file (its optimizer is not SGD: it carries optimizer state)");
+        const uint64_t body = blob_body_bytes(FWGPU_OPT_SGD, mi->dequantize_weights == 1, s);
+        if (in.remaining() != body) return fail(FWGPU_ERR_FORMAT, "image_load: the weights section's length differs from the model's");
+        const long header_bytes = std::ftell(in.f);
+        if (header_bytes < 0) return fail(FWGPU_ERR_IO, "image_load: ftell failed");
+        std::unique_ptr<fwgpu_image, void (*)(fwgpu_image *)> img(new fwgpu_image(), fwgpu_image_free);
+        img->device = device;
+        img->header.resize((size_t)header_bytes);
+        std::rewind(in.f);
+        in.need(img->header.data(), img->header.size(), "header");
+        std::vector<uint8_t> w(body);
+        in.need(w.data(), body, "weights");
+        img->weights_bytes = body;
+        FWGPU_HIP(hipSetDevice(device));
+        if ((rc = image_alloc(img.get()))) return rc;
+        FWGPU_HIP(hipMemcpy(img->d_weights, w.data(), body, hipMemcpyHostToDevice));
+        *out = img.release();
+        return FWGPU_OK;
+    } catch (const std::exception &e) {
+        return fail(FWGPU_ERR_FORMAT, e.what());
+    }
+}
+
+int fwgpu_image_len(const fwgpu_image *img, uint64_t *header_bytes, uint64_t *weights_bytes) {
+    if (!img) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (header_bytes) *header_bytes = img->header.size();
+    if (weights_bytes) *weights_bytes = img->weights_bytes;
+    return FWGPU_OK;
+}
+
+int fwgpu_image_read(const fwgpu_image *img, uint8_t *out, uint64_t cap) {
+    if (!img || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (cap < img->header.size() + img->weights_bytes) return fail(FWGPU_ERR_RANGE, "image_read: buffer too small");
+    std::memcpy(out, img->header.data(), img->header.size());
+    FWGPU_HIP(hipSetDevice(img->device));
+    if (img->weights_bytes) FWGPU_HIP(hipMemcpy(out + img->header.size(), img->d_weights, img->weights_bytes, hipMemcpyDeviceToHost));
+    return FWGPU_OK;
+}
+
 // persistence.rs:91-125: header + vw_source + ModelInstance, no weights, no device
 int fwgpu_model_read_header(const char *path, fwgpu_vwmap **vw_out, fwgpu_model_instance **mi_out) {
     if (!path) return fail(FWGPU_ERR_INVALID, "NULL argument");
@@ -836,6 +984,7 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, 
                                               ", expected " + std::to_string(s.elems()));
         const int file_opt = mi->optimizer;
         const bool quantized = mi->dequantize_weights == 1;
+        const long header_bytes = std::ftell(in.f);  // the file's bytes before its weights section (fwgpu_packed_apply_diff)
         const uint64_t body = blob_body_bytes(file_opt, quantized, s);
         if (in.remaining() < body) return fail(FWGPU_ERR_FORMAT, "model file: truncated weights");
         std::vector<uint8_t> src(body);
@@ -856,6 +1005,9 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, 
         fwgpu_regressor *r = nullptr;
         rc = fwgpu::create_packed(&cfg, lr_w.data(), ffm, &r);
         if (rc) return rc;
+        // a quantised inference file's weights section is what the tables hold, byte for byte: a diff of two such files patches them
+        r->file_quantized_at_load = !quantized;
+        r->file_header_bytes = quantized && sgd && header_bytes > 0 ? (uint64_t)header_bytes : 0;
         fill_views(mi.get());
         *r_out = r;
         if (vw_out) *vw_out = vw.release();

@@ -805,4 +805,16 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *ptr, uint64_t *lines, ui
     return FWGPU_OK;
 }
 
+// The hot patch of a --packed_weights model from a byte diff of two published files (fwgpu_packed_apply_diff), under the model's mutex.  The
+// prototype and every clone_lite copy share the tables, so all of them see it; such predictors keep no device cache, so nothing derived from
+// the weights goes stale.
+int fwgpu_predictor_apply_diff(FfiPredictor *ptr, const uint8_t *diff, uint64_t len) {
+    if (!ptr || (len && !diff)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    SharedModel &m = *ptr->model;
+    if (!m.re->packed())
+        return fail(FWGPU_ERR_INVALID, "predictor_apply_diff: the predictor was not created with --packed_weights: its f32 tables are not the file's bytes, load the file");
+    std::lock_guard<std::mutex> g(m.mu);
+    return fwgpu_packed_apply_diff(m.re, diff, len, nullptr);
+}
+
 }  // extern "C"

@@ -165,3 +165,116 @@ def dequantize_ffm_weights(blob: bytes, n: int) -> np.ndarray:  # quantization.r
     out = np.zeros(n, dtype=np.float32)
     capi.check(capi.lib().fwgpu_dequantize_ffm_weights(capi.ptr(src), n, capi.ptr(out)))
     return out
+
+
+# ---- byte diffs of published inference files (weight_patcher/src/main.rs; the bare stream, without the tool's gzip container)
+def _two_call(call, first_cap: int = 0) -> tuple:
+    """the library's two-call protocol: the size first (or a first try with first_cap bytes, which a small stream fits), then the bytes
+    -> (stream, changed)"""
+    n, changed = C.c_uint64(0), C.c_uint64(0)
+    first = np.zeros(first_cap, dtype=np.uint8)
+    rc = call(capi.ptr(first), first.size, C.byref(n), C.byref(changed))
+    if rc == capi.OK:
+        return first[: n.value].tobytes(), changed.value
+    if rc != capi.ERR_RANGE:
+        capi.check(rc)
+    if n.value == 0:
+        return b"", changed.value
+    out = np.zeros(n.value, dtype=np.uint8)
+    capi.check(call(capi.ptr(out), out.size, C.byref(n), C.byref(changed)))
+    return out[: n.value].tobytes(), changed.value
+
+
+def diff_bytes(a: bytes, b: bytes, base_offset: int = 0, prev_index: int = 0, with_changed: bool = False):
+    """compare_files_and_write_diff (main.rs:68-130) on two byte strings of one length that stand for the files' bytes from base_offset on;
+    prev_index: the index of the last entry emitted before them -- fwgpu_diff_bytes"""
+    x, y = np.frombuffer(a, dtype=np.uint8), np.frombuffer(b, dtype=np.uint8)
+    if x.size != y.size:
+        raise ValueError("diff_bytes: the inputs have different lengths")
+    L = capi.lib()
+    stream, changed = _two_call(lambda out, cap, n, ch: L.fwgpu_diff_bytes(capi.ptr(x), capi.ptr(y), x.size, base_offset, prev_index, out, cap, n, ch))
+    return (stream, changed) if with_changed else stream
+
+
+def apply_diff_bytes(target: bytes, diff: bytes, base_offset: int = 0) -> bytes:
+    """recreate_file_inner (main.rs:148-206): the second file's bytes from the first's and the stream; a bad stream raises with
+    ERR_FORMAT -- fwgpu_diff_apply_bytes"""
+    t = np.frombuffer(target, dtype=np.uint8).copy()
+    d = np.frombuffer(diff, dtype=np.uint8)
+    capi.check(capi.lib().fwgpu_diff_apply_bytes(capi.ptr(t), t.size, base_offset, capi.ptr(d), d.size, None))
+    return t.tobytes()
+
+
+class Image:
+    """fwgpu_image: the file save_inference_regressor would write at this moment, its header on the host and its weights section in one
+    device allocation.  A trainer keeps the last published one and diffs the next against it on the device."""
+
+    def __init__(self, h):
+        self.L = capi.lib()
+        self.h = h
+
+    @classmethod
+    def capture(cls, mi: ModelInstance, vwmap: VwNamespaceMap, re: Regressor, quantize_weights: bool = False, extra=None):
+        mh = ModelInstanceHandle.from_model_instance(mi, extra)
+        h = C.c_void_p()
+        try:
+            capi.check(capi.lib().fwgpu_image_capture(re.h, vwmap.h, mh.h, int(quantize_weights), C.byref(h)))
+        finally:
+            mh.close()
+        return cls(h)
+
+    @classmethod
+    def load(cls, filename: str, device: int = 0):
+        h = C.c_void_p()
+        capi.check(capi.lib().fwgpu_image_load(filename.encode(), device, C.byref(h)))
+        return cls(h)
+
+    def lengths(self):
+        """(header_bytes, weights_bytes)"""
+        hb, wb = C.c_uint64(0), C.c_uint64(0)
+        capi.check(self.L.fwgpu_image_len(self.h, C.byref(hb), C.byref(wb)))
+        return hb.value, wb.value
+
+    def read(self) -> bytes:
+        out = np.zeros(sum(self.lengths()), dtype=np.uint8)
+        capi.check(self.L.fwgpu_image_read(self.h, capi.ptr(out), out.size))
+        return out.tobytes()
+
+    def diff(self, nxt: "Image", with_changed: bool = False):
+        """the stream that turns this image's file into nxt's (diff_bytes of the two files), made on the device -- fwgpu_image_diff"""
+        stream, changed = _two_call(lambda out, cap, n, ch: self.L.fwgpu_image_diff(self.h, nxt.h, out, cap, n, ch), first_cap=1 << 20)  # (one call when little changed)
+        return (stream, changed) if with_changed else stream
+
+    def close(self):
+        if self.h:
+            self.L.fwgpu_image_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_diff(a: bytes, b: bytes, base_offset: int = 0, prev_index: int = 0, device: int = 0):
+    """the diff's three kernels alone on two byte strings of one length (fwgpu_debug_diff) -> (stream, changed)"""
+    x, y = np.frombuffer(a, dtype=np.uint8), np.frombuffer(b, dtype=np.uint8)
+    if x.size != y.size:
+        raise ValueError("debug_diff: the inputs have different lengths")
+    L = capi.lib()
+    return _two_call(lambda out, cap, n, ch: L.fwgpu_debug_diff(device, capi.ptr(x), capi.ptr(y), x.size, base_offset, prev_index, out, cap, n, ch))
+
+
+def debug_diff_geometry() -> int:
+    """the bytes of one tile of the diff kernels (fwgpu_debug_diff_geometry)"""
+    t = C.c_uint32(0)
+    capi.check(capi.lib().fwgpu_debug_diff_geometry(C.byref(t)))
+    return t.value
+
+
+def debug_diff_rates(base: Image, nxt: Image):
+    """milliseconds by device events: (size pass, tile scan, emit pass, device-to-device copy of one weights section) -- fwgpu_debug_diff_rates"""
+    ms = np.zeros(4, dtype=np.float32)
+    capi.check(capi.lib().fwgpu_debug_diff_rates(base.h, nxt.h, capi.ptr(ms)))
+    return tuple(float(x) for x in ms)

@@ -563,6 +563,15 @@ class Regressor:
             return into
         return Regressor.from_handle(replace(self.mi, optimizer=Optimizer.SGD, wiring=capi.WIRING_REGRESSOR), h)
 
+    def apply_diff(self, diff: bytes) -> int:
+        """patches a packed regressor loaded from an already quantised inference file (persistence.new_regressor_from_filename(packed=True))
+        in place from the byte-diff stream of that file and the next published one: afterwards it is the regressor loaded from the next
+        file.  Returns the number of entries -- fwgpu_packed_apply_diff"""
+        d = np.frombuffer(diff, dtype=np.uint8)
+        n = C.c_uint64(0)
+        check(self.L.fwgpu_packed_apply_diff(self.h, ptr(d), d.size, C.byref(n)))
+        return n.value
+
     def table_len(self, which):
         n = C.c_uint64(0)
         check(self.L.fwgpu_table_len(self.h, which, C.byref(n)))

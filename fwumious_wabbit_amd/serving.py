@@ -28,6 +28,8 @@ def _lib():
         L.fwgpu_predictor_predict_requests.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_uint32),
                                                        C.POINTER(C.c_void_p)]
         L.fwgpu_predictor_predict_requests.restype = C.c_int
+        L.fwgpu_predictor_apply_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.fwgpu_predictor_apply_diff.restype = C.c_int
         L._fw_ffi_ready = True
     return L
 
@@ -95,6 +97,12 @@ class Predictor:
         n, h, f = C.c_uint64(), C.c_uint64(), C.c_int()
         capi.check(self.L.fwgpu_predictor_last_text_route(self.p, C.byref(n), C.byref(h), C.byref(f)))
         return n.value, h.value, bool(f.value)
+
+    def apply_diff(self, diff: bytes):
+        """patches a --packed_weights model in place from the byte-diff stream of the file it was loaded from and the next published file
+        (persistence.Image.diff / diff_bytes); the prototype and every clone_lite copy see it -- fwgpu_predictor_apply_diff"""
+        d = np.frombuffer(diff, dtype=np.uint8)
+        capi.check(self.L.fwgpu_predictor_apply_diff(self.p, capi.ptr(d), d.size))
 
     def close(self):
         if self.p:

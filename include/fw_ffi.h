@@ -57,6 +57,12 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint
 int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs,
                                      const uint32_t *n_inputs, float *const *out);
 
+/* Not in the reference's FFI (its weight_patcher rewrites the file): patches a --packed_weights model in place from the bare byte-diff stream
+ * of the file it was loaded from and the next published file (include/fwgpu.h: fwgpu_image_diff, fwgpu_diff_bytes; fwgpu_packed_apply_diff
+ * states the refusals).  Runs under the model's mutex; the prototype and every clone_lite copy share the tables and see the patch.
+ * Predictors without --packed_weights are FWGPU_ERR_INVALID.  A refused or malformed stream leaves the model as it was. */
+int fwgpu_predictor_apply_diff(FfiPredictor *p, const uint8_t *diff, uint64_t len);
+
 #ifdef __cplusplus
 }
 #endif

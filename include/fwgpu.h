@@ -887,6 +887,57 @@ int fwgpu_model_convert_inference(const char *in_path, const char *out_path, int
 int fwgpu_quantize_ffm_weights(const float *weights, uint64_t n, uint8_t *out, uint64_t cap);
 int fwgpu_dequantize_ffm_weights(const uint8_t *in, uint64_t n, float *weights);
 
+/* ---------------------------------------------------------------- byte diffs of published inference models (weight_patcher/src/main.rs)
+ * THE STREAM is what the reference's compare_files_and_write_diff hands to its writer, byte for byte, WITHOUT the gzip container the tool
+ * wraps around it: for every index i with a[i] != b[i], ascending, varint(i - prev) then the byte b[i]; prev is the previous entry's index
+ * and starts at 0 (a difference at index 0 is delta 0); the varint is little-endian base-128, top bit set on every byte but the last.
+ * THE READER IS STRICTER than recreate_file_inner: a stream that ends inside an entry, a varint of more than 10 bytes or beyond 64 bits, an
+ * entry at or beyond the target's end, and a zero delta in any entry but the first are FWGPU_ERR_FORMAT, and nothing is written unless the
+ * whole stream is valid (csrc/diff_stream.h holds the codec and states the format). */
+/* compare_files_and_write_diff (main.rs:68-130) on two host arrays that stand for the bytes [base_offset, base_offset + n) of two files.
+ * prev_index: the index of the last entry already emitted before this range (0 at the start of a file; above base_offset is
+ * FWGPU_ERR_INVALID).  Two-call protocol: out == NULL or cap too small returns FWGPU_ERR_RANGE with *written = the size needed.
+ * *changed (may be NULL): the number of entries. */
+int fwgpu_diff_bytes(const uint8_t *a, const uint8_t *b, uint64_t n, uint64_t base_offset, uint64_t prev_index, uint8_t *out, uint64_t cap,
+                     uint64_t *written, uint64_t *changed);
+/* recreate_file_inner (main.rs:148-206) in place on a host array that stands for the file's bytes [base_offset, base_offset + n).  Entries
+ * below base_offset are skipped; *applied (may be NULL): entries written.  A bad stream is FWGPU_ERR_FORMAT and the target is unchanged. */
+int fwgpu_diff_apply_bytes(uint8_t *target, uint64_t n, uint64_t base_offset, const uint8_t *diff, uint64_t len, uint64_t *applied);
+/* An image is the file fwgpu_model_save_inference(path, vw, mi, r, quantize_weights) would write at this moment, split in two: the header
+ * (write_header + the u64 element count) on the host, the weights section in ONE device allocation in file order.  It is built by the routines
+ * that call uses (the LR compaction, the device quantiser with its host route, the layers' copies); the tables do not cross to the host.
+ * CONTRACT: fwgpu_image_read gives exactly that file's bytes.  capture waits for the regressor's outstanding launches, leaves it and its ability
+ * to train untouched, and refuses packed regressors.  fwgpu_image_load puts an existing inference file (optimizer SGD, weights only) into the
+ * same form: a trainer that restarts diffs its next publish against it. */
+typedef struct fwgpu_image fwgpu_image;
+int fwgpu_image_capture(fwgpu_regressor *r, const fwgpu_vwmap *vw, const fwgpu_model_instance *mi, int quantize_weights, fwgpu_image **img);
+int fwgpu_image_load(const char *path, int device, fwgpu_image **img);
+int fwgpu_image_len(const fwgpu_image *img, uint64_t *header_bytes, uint64_t *weights_bytes);
+int fwgpu_image_read(const fwgpu_image *img, uint8_t *out, uint64_t cap);  /* cap below header + weights bytes: FWGPU_ERR_RANGE */
+void fwgpu_image_free(fwgpu_image *img);
+/* The stream of the two whole files (compare_files_and_write_diff on them): the headers are diffed on the host, the weights sections by
+ * three HIP kernels (csrc/patch.hip: size pass, tile scan, emit pass) with base_offset = header_bytes, and only the stream crosses to the
+ * host.  Two-call protocol as fwgpu_diff_bytes.  *changed (may be NULL): differing bytes -- when the quantiser's rounded extremes move, nearly
+ * every bucket changes and the stream approaches two bytes per file byte: ship the file instead.  Images of different lengths or on
+ * different devices are FWGPU_ERR_INVALID. */
+int fwgpu_image_diff(const fwgpu_image *base, const fwgpu_image *next, uint8_t *out, uint64_t cap, uint64_t *written, uint64_t *changed);
+/* Patches a packed regressor in place from such a stream: afterwards it is the regressor fwgpu_model_load_packed makes from the second file.
+ * r must come from fwgpu_model_load_packed on an inference file that was already quantised (dequantize_weights = true): its tables are
+ * that file's bytes.  FWGPU_ERR_INVALID, with the reason: an f32 regressor, a product of fwgpu_pack_regressor (no file behind it: refresh it
+ * with that call), a packed regressor whose file was quantised at load, and a stream with an entry in the file's header ("the model's header
+ * changed: load the file").  A bad stream is FWGPU_ERR_FORMAT.  In all these cases r is as it was and usable.  Entries in the FFM block's 8-byte
+ * header update the two launch constants; all others are scattered by one kernel, byte by byte.  The call waits for the device; the caller
+ * must not have predict launches of r in flight on other streams (fwgpu_pack_regressor's refresh contract).  *applied (may be NULL): entries. */
+int fwgpu_packed_apply_diff(fwgpu_regressor *r, const uint8_t *diff, uint64_t len, uint64_t *applied);
+/* debug: two host arrays uploaded, the three kernels run, the stream returned (two-call protocol as fwgpu_diff_bytes) */
+int fwgpu_debug_diff(int device, const uint8_t *a, const uint8_t *b, uint64_t n, uint64_t base_offset, uint64_t prev_index, uint8_t *out,
+                     uint64_t cap, uint64_t *written, uint64_t *changed);
+/* debug: the bytes of one tile of the kernels, so that tests can place differences on tile edges */
+int fwgpu_debug_diff_geometry(uint32_t *tile_bytes);
+/* debug (scripts/bench_publish_diff.py): milliseconds, by device events, of the size pass, the tile scan, the emit pass and a device-to-device
+ * copy of one weights section; nothing of the images changes */
+int fwgpu_debug_diff_rates(const fwgpu_image *base, const fwgpu_image *next, float *ms4);
+
 /* ---------------------------------------------------------------- synthetic record streams
  * Generates records in the parser's output format (parser.rs:57-74) for the BASELINE.json configs:
  * n_namespaces namespaces == fields; per namespace 1+Poisson(mean_extra) features (exactly 1 when
