@@ -26,7 +26,7 @@ TABLE_LR, TABLE_FFM_W, TABLE_FFM_ACC, TABLE_NN_W, TABLE_NN_ACC = 0, 1, 2, 3, 4
 # fwgpu_debug_last_route
 ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK, ROUTE_REQUESTS = 0, 1, 2, 3, 4, 5, 6
 # fwgpu_debug_last_launch
-KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED, KERNEL_REQUESTS = 0, 1, 2, 3, 4
+KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED, KERNEL_REQUESTS, KERNEL_PACKED_REQUESTS = 0, 1, 2, 3, 4, 5
 LAUNCH_INFO = ("family", "chunks", "window", "chain", "no_kept_rows", "lds_keep", "threads", "lds_bytes")
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
@@ -255,6 +255,10 @@ def lib():
         "fwgpu_model_load": [C.c_char_p, i32, i32, P(vp), P(vp), P(vp)],
         "fwgpu_model_load_packed": [C.c_char_p, i32, P(vp), P(vp), P(vp)],
         "fwgpu_ffm_storage": [vp, P(i32), P(u64)],
+        "fwgpu_packed_enable_caches": [vp],
+        "fwgpu_packed_caches_state": [vp, P(i32), P(u64)],
+        "fwgpu_debug_block_cache_read": [vp, vp, vp, vp, P(u64)],
+        "fwgpu_debug_requests_time": [vp, vp, i32, u32, P(f32)],
         "fwgpu_quantize_ffm_table": [vp, vp, u64, P(u64)],
         "fwgpu_model_save_inference": [C.c_char_p, vp, vp, vp, i32],
         "fwgpu_pack_regressor": [vp, P(vp)],

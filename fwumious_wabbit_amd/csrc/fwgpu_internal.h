@@ -418,6 +418,8 @@ struct RequestsParams {
     uint32_t F, k, R;
     uint32_t slots;                 // LDS slices of R floats per wave: min(F, the batch's largest FFM entry count)
     int32_t has_lr;
+    const uint16_t *ffm_q;          // a packed regressor's table of f16 bucket numbers (then ffm_w is NULL), else NULL
+    float q_increment, q_min;       // ... and its header, as the regressor holds it at the launch: w = q_min + f32(bucket) * q_increment
 };
 struct RequestsShape {
     uint32_t slots = 0, threads = 0, chunks = 0;
@@ -425,7 +427,21 @@ struct RequestsShape {
 };
 // false: one wave's slices do not fit lds_limit bytes
 bool requests_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out);
-hipError_t launch_requests(const RequestsParams &p, const RequestsShape &shape, hipStream_t stream);
+// rows: rows of a field in flight per lane on a packed table -- 0 = the default, 4 or 8 (an f32 table always runs its own depth)
+hipError_t launch_requests(const RequestsParams &p, const RequestsShape &shape, hipStream_t stream, int rows = 0);
+// fwgpu_setup_cache on a packed regressor (fwgpu_packed_enable_caches): the context's entries, ordered by field, -> the cache's T, dcf and cnt
+struct PackedCacheBuild {
+    const uint16_t *ffm_q;
+    const uint32_t *ffm_hash;       // [n] the context's entries as an entry batch holds them
+    const float *ffm_val;
+    const uint8_t *ffm_fld;
+    uint32_t n;
+    uint32_t F, k, R;
+    float q_increment, q_min;
+    float *T, *dcf;                 // [F * R], [F]
+    uint32_t *cnt;                  // [F]
+};
+hipError_t launch_packed_cache_build(const PackedCacheBuild &p, hipStream_t stream);
 // The window table of one stream of examples, on the device.  score() sizes it for the launch's last window (growing geometrically: a new
 // allocation, the old rows copied on the stream, the stream waited for once before the old one is freed) and enqueues the kernel; no other
 // call of it allocates.  fetch() waits for the stream.
@@ -499,6 +515,9 @@ struct fwgpu_batch {
     const float *const *req_T = nullptr;
     float *req_base = nullptr;
     uint32_t *req_of = nullptr;
+    uint32_t req_of_n = 0;      // examples the index array covers
+    const float *req_single_T = nullptr;  // ... and that cache's d_T, as the table holds it
+    bool req_single = false;    // the set is ONE cache attached through fwgpu_batch_set_cache (packed regressors with caches enabled)
 };
 
 struct fwgpu_regressor {
@@ -517,6 +536,10 @@ struct fwgpu_regressor {
     // where the packed tables came from (fwgpu_packed_apply_diff): a quantised inference file's own bytes can be patched from a diff of two such files
     uint64_t file_header_bytes = 0;     // that file's bytes before its weights section; 0: no such file (fwgpu_pack_regressor, or quantised at load)
     bool file_quantized_at_load = false;
+    // fwgpu_packed_enable_caches: the one-way switch, and the weights epoch the caches are held to (bumped by fwgpu_packed_apply_diff and by
+    // fwgpu_pack_regressor's refresh in place)
+    bool packed_caches = false;
+    uint64_t weights_epoch = 0;
     int placement_tries = 0;                     // candidate allocations timed for d_ffm_acc (regressor.cpp: place_ffm_acc)
     float placement_ms_lo = 0, placement_ms_hi = 0;  // fastest / slowest pair probe among them
     float placement_ms_single = 0;                    // the same probe on the weight table alone
@@ -561,6 +584,7 @@ struct fwgpu_split {
 // Vec<BlockCache> of the reference (regressor.rs:40-50): what setup_cache leaves behind for predict_with_cache
 struct fwgpu_block_cache {
     fwgpu_regressor *owner = nullptr;
+    uint64_t epoch = 0;      // the owner's weights epoch at the last fwgpu_setup_cache (packed regressors: a cache of an older epoch is stale)
     float *d_T = nullptr;    // [F*R] + [F] (dcf) + [F] (cnt) in one allocation
     float *d_dcf = nullptr;
     uint32_t *d_cnt = nullptr;  // cached features per field, as the setup launch counted them (a repeated feature counts twice, as in the field sums)

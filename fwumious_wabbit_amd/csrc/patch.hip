@@ -534,6 +534,7 @@ int fwgpu_packed_apply_diff(fwgpu_regressor *r, const uint8_t *diff, uint64_t le
     }
     memcpy(&r->q_increment, q_header, 4);
     memcpy(&r->q_min, q_header + 4, 4);
+    r->weights_epoch++;  // (context caches set up before, fwgpu_packed_enable_caches, are stale from here on)
     if (applied) *applied = entries;
     return FWGPU_OK;
 }

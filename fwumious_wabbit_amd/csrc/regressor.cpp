@@ -570,7 +570,7 @@ static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int up
 // Why the requests kernels (requests.hip) do not serve this regressor / batch shape, or NULL.  Asked when a set is attached and again at every launch.
 static const char *requests_refusal(const fwgpu_regressor *r, const fwgpu_batch *b) {
     const uint32_t k = r->cfg.ffm_k, F = r->cfg.ffm_num_fields;
-    if (r->packed()) return "a packed regressor keeps no device-side context cache";
+    if (r->packed() && !r->packed_caches) return "a packed regressor keeps no device-side context cache";
     if (r->nn.n_layers) return "models with a deep head are not served by the requests route (fwgpu_batch_set_cache serves them)";
     if (b->records) return "a record batch is not served by the requests route (an entry batch of the filtered buffers is)";
     if (b->host_copy) return "the batch holds an oversize example (more than 4096 entries of a kind, or beyond the fused kernel's LDS)";
@@ -589,20 +589,35 @@ static void requests_detach(fwgpu_batch *b) {
     b->req_T = nullptr;
     b->req_base = nullptr;
     b->req_of = nullptr;
+    b->req_of_n = 0;
+    b->req_single = false;
     b->req_caches.clear();
 }
 
+// A packed regressor's caches hold sums of the weights of ONE epoch (fwgpu_packed_apply_diff and fwgpu_pack_regressor's refresh bump it): an older
+// cache is refused wherever it is attached or launched with, until fwgpu_setup_cache on its handle has refilled it.
+static bool cache_is_stale(const fwgpu_regressor *r, const fwgpu_block_cache *c) { return r->packed() && c->epoch != r->weights_epoch; }
+static const char *kStaleCache =
+    "a context cache is stale: the packed regressor's weights changed after it was set up (fwgpu_packed_apply_diff, fwgpu_pack_regressor); "
+    "call fwgpu_setup_cache on the same handle";
+
 // predict-only launch of an entry batch with a cache per example: base(S) of every cache of the set, then one wavefront per candidate, on `stream`
-static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream) {
+// (`rows`: the packed predict kernel's rows in flight, 0 = its default -- fwgpu_debug_requests_time)
+static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream, int rows = 0) {
     if (update) return fail(FWGPU_ERR_INVALID, "a batch with a cache per example (fwgpu_batch_set_caches) is predict-only: update must be 0");
     if (const char *why = requests_refusal(r, b)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + why);
+    for (const fwgpu_block_cache *c : b->req_caches)
+        if (cache_is_stale(r, c)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + kStaleCache);
     const uint32_t F = r->cfg.ffm_num_fields, k = r->cfg.ffm_k, R = F * k;
     RequestsShape shape;
     if (!requests_launch_shape(F, R, b->max_ffm, r->lds_per_cu, &shape))
         return fail(FWGPU_ERR_RANGE, "requests route: min(fields, the batch's largest FFM entry count) * F * k floats of one candidate do not fit the 160 KiB LDS");
     RequestsParams p{};
-    p.ffm_w = r->d_ffm_w;
-    p.lr = r->d_lr;
+    p.ffm_w = r->packed() ? nullptr : r->d_ffm_w;
+    p.ffm_q = r->d_ffm_q;  // (packed: 16-bit buckets and the header as it is NOW -- a refresh or a hot patch is seen by this launch)
+    p.q_increment = r->q_increment;
+    p.q_min = r->q_min;
+    p.lr = r->d_lr;        // (a packed regressor keeps its LR weights as {w, 0} pairs: the same layout)
     p.ffm_hash = b->ffm_hash;
     p.ffm_val = b->ffm_val;
     p.ffm_fld = b->ffm_fld;
@@ -621,17 +636,21 @@ static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hi
     p.R = R;
     p.slots = shape.slots;
     p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
-    r->last_launch[0] = FWGPU_KERNEL_REQUESTS;
+    r->last_launch[0] = r->packed() ? FWGPU_KERNEL_PACKED_REQUESTS : FWGPU_KERNEL_REQUESTS;
     r->last_launch[1] = (int32_t)shape.chunks;
     r->last_launch[2] = r->last_launch[3] = r->last_launch[4] = r->last_launch[5] = 0;
     r->last_launch[6] = (int32_t)shape.threads;
     r->last_launch[7] = (int32_t)shape.lds_bytes;
-    FWGPU_HIP(launch_requests(p, shape, stream));
+    FWGPU_HIP(launch_requests(p, shape, stream, rows));
     return FWGPU_OK;
 }
 
 // (`route`: where fwgpu_learn_batch records the path the launch took -- fwgpu_debug_last_route; the single-example calls pass none)
 static int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream, int32_t *route = nullptr) {
+    if (r->packed() && r->packed_caches && b->n && !b->req_caches.empty()) {  // fwgpu_packed_enable_caches: one cache (fwgpu_batch_set_cache) or a set
+        if (route) *route = FWGPU_ROUTE_REQUESTS;
+        return run_batch_requests(r, b, update, stream);
+    }
     if (route) *route = FWGPU_ROUTE_PACKED;
     if (r->packed()) return run_batch_packed(r, b, mode, update, stream);
     if (route) *route = FWGPU_ROUTE_NONE;
@@ -1589,13 +1608,15 @@ int fwgpu_learn_batch_sync(fwgpu_regressor *r, fwgpu_batch *b, fwgpu_split *sp, 
 // reference (prepare_forward_cache skips every feature: `hash & IS_NOT_SINGLE_MASK == 0` always holds for a masked hash,
 // block_lr.rs:236-239), so LR entries are always all read, exactly like there.
 
+static int requests_attach_single(fwgpu_batch *b, const fwgpu_block_cache *c);
 static uint64_t cache_key(const fwgpu_ffm_entry &e) { return ((uint64_t)e.hash << 32) | e.contra_field_index; }  // regressor.rs:25-38
 
 int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_lr, const fwgpu_ffm_entry *ffm,
                       uint32_t n_ffm, fwgpu_block_cache **cache) {
     if (!r || !cache) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if ((n_lr && !lr) || (n_ffm && !ffm)) return fail(FWGPU_ERR_INVALID, "NULL entry buffer");
-    if (int rcp = refuse_packed(r, "setup_cache (a device-side context cache)")) return rcp;
+    if (!r->packed_caches)
+        if (int rcp = refuse_packed(r, "setup_cache (a device-side context cache)")) return rcp;
     FWGPU_HIP(hipSetDevice(r->device));
     const uint32_t F = r->cfg.ffm_k ? r->cfg.ffm_num_fields : 0, R = F * r->cfg.ffm_k;
     fwgpu_block_cache *c = *cache;
@@ -1616,7 +1637,30 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
     int rc = append_example(r, hb, lr, n_lr, ffm, n_ffm, 0.0f, 1.0f);
     if (rc == FWGPU_OK) rc = ensure_one(r, (uint32_t)hb.lr_hash.size(), (uint32_t)hb.ffm_hash.size());
     if (rc == FWGPU_OK) rc = batch_upload(r->one, hb, 0);
-    if (rc == FWGPU_OK) {
+    if (rc == FWGPU_OK && r->packed()) {
+        // packed weights: the build kernel of requests.hip in place of the example kernel's emitting launch -- the same sums in the same order
+        if (!hb.aligned4)
+            rc = fail(FWGPU_ERR_INVALID, "packed regressor: an FFM entry's hash is not a multiple of 4 (rows must start where the translator's mask puts them: hash & fwgpu_ffm_hash_mask)");
+        if (rc == FWGPU_OK) {
+            PackedCacheBuild q{};
+            q.ffm_q = r->d_ffm_q;
+            q.ffm_hash = r->one->ffm_hash;
+            q.ffm_val = r->one->ffm_val;
+            q.ffm_fld = r->one->ffm_fld;
+            q.n = (uint32_t)hb.ffm_hash.size();
+            q.F = F;
+            q.k = r->cfg.ffm_k;
+            q.R = R;
+            q.q_increment = r->q_increment;
+            q.q_min = r->q_min;
+            q.T = c->d_T;
+            q.dcf = c->d_dcf;
+            q.cnt = c->d_cnt;
+            hipError_t e = launch_packed_cache_build(q, 0);
+            if (e == hipSuccess) e = hipStreamSynchronize(0);
+            if (e != hipSuccess) rc = fail(FWGPU_ERR_DEVICE, std::string("setup_cache (packed): ") + hipGetErrorString(e));
+        }
+    } else if (rc == FWGPU_OK) {
         r->one->cache = nullptr;
         r->one->emit_T = c->d_T;
         r->one->emit_dcf = c->d_dcf;
@@ -1625,7 +1669,7 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
         r->one->emit_T = r->one->emit_dcf = nullptr;
         r->one->emit_cnt = nullptr;
     }
-    if (rc == FWGPU_OK && one_prediction(r, &pred) != FWGPU_OK) rc = fail(FWGPU_ERR_DEVICE, "setup_cache: launch failed");
+    if (rc == FWGPU_OK && !r->packed() && one_prediction(r, &pred) != FWGPU_OK) rc = fail(FWGPU_ERR_DEVICE, "setup_cache: launch failed");
     if (rc != FWGPU_OK) {
         if (!*cache) {
             (void)hipFree(c->d_T);
@@ -1637,6 +1681,7 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
     for (uint32_t i = 0; i < (r->cfg.ffm_k ? n_ffm : 0); i++) c->present.push_back(cache_key(ffm[i]));
     std::sort(c->present.begin(), c->present.end());
     c->present.erase(std::unique(c->present.begin(), c->present.end()), c->present.end());
+    c->epoch = r->weights_epoch;
     *cache = c;
     return FWGPU_OK;
 }
@@ -1665,6 +1710,7 @@ int fwgpu_predict_with_cache(fwgpu_regressor *r, const fwgpu_block_cache *c, con
     if (!r || !c || !prediction) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (c->owner != r) return fail(FWGPU_ERR_INVALID, "cache belongs to another regressor");
     if ((n_lr && !lr) || (n_ffm && !ffm)) return fail(FWGPU_ERR_INVALID, "NULL entry buffer");
+    if (cache_is_stale(r, c)) return fail(FWGPU_ERR_INVALID, std::string("predict_with_cache: ") + kStaleCache);
     FWGPU_HIP(hipSetDevice(r->device));
     std::vector<fwgpu_ffm_entry> rest(n_ffm);
     uint32_t m = 0;
@@ -1678,9 +1724,15 @@ int fwgpu_predict_with_cache(fwgpu_regressor *r, const fwgpu_block_cache *c, con
     if (rc) return rc;
     rc = batch_upload(r->one, hb, 0);
     if (rc) return rc;
-    r->one->cache = c;
-    rc = run_batch(r, r->one, FWGPU_MODE_SEQUENTIAL, 0, 0);
-    r->one->cache = nullptr;
+    if (r->packed()) {  // the set of one on the requests route; the table stays allocated for the next call, the set does not stay attached
+        rc = requests_attach_single(r->one, c);
+        if (rc == FWGPU_OK) rc = run_batch(r, r->one, FWGPU_MODE_SEQUENTIAL, 0, 0);
+        r->one->req_caches.clear();
+    } else {
+        r->one->cache = c;
+        rc = run_batch(r, r->one, FWGPU_MODE_SEQUENTIAL, 0, 0);
+        r->one->cache = nullptr;
+    }
     if (rc) return rc;
     return one_prediction(r, prediction);
 }
@@ -1693,6 +1745,9 @@ static inline uint32_t present_bit(uint64_t key) { return (uint32_t)((key * 0x9e
 // fwgpu_block_cache_filter drops, PROVIDED the request passes fwgpu_block_cache_record_ok.
 int fwgpu_block_cache_cover_record(fwgpu_block_cache *c, const fwgpu_translator_config *t, const uint32_t *record, uint32_t len) {
     if (!c || !t || !record) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (c->owner && c->owner->packed())
+        return fail(FWGPU_ERR_INVALID, "block_cache_cover_record: a packed regressor's cache serves the entry route only (an entry batch of the buffers "
+                                       "fwgpu_block_cache_filter leaves, fwgpu_batch_set_cache / fwgpu_batch_set_caches); record batches with a cache are not served");
     uint32_t nl = 0, nf = 0;
     int rc = count_record(t, record, len, &nl, &nf);
     if (rc) return rc;
@@ -1774,6 +1829,14 @@ extern "C" {
 int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *c) {
     if (!b) return fail(FWGPU_ERR_INVALID, "NULL batch");
     if (c && c->owner != b->owner) return fail(FWGPU_ERR_INVALID, "cache belongs to another regressor");
+    if (c && b->owner && b->owner->packed()) {  // (fwgpu_packed_enable_caches: a packed regressor has no other cache) the set of ONE on the requests route
+        if (b->records)
+            return fail(FWGPU_ERR_INVALID, "set_cache: a packed regressor serves a cache through the entry route only: a record batch with a cache is not served "
+                                           "(send an entry batch of the buffers fwgpu_block_cache_filter leaves)");
+        if (const char *why = requests_refusal(b->owner, b)) return fail(FWGPU_ERR_INVALID, std::string("set_cache: ") + why);
+        if (cache_is_stale(b->owner, c)) return fail(FWGPU_ERR_INVALID, std::string("set_cache: ") + kStaleCache);
+        return requests_attach_single(b, c);
+    }
     if (c && b->records && !c->d_cover)
         return fail(FWGPU_ERR_INVALID, "a record batch needs a context cache that knows the context's record (fwgpu_block_cache_cover_record)");
     b->cache = c;
@@ -1798,6 +1861,7 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
     for (uint32_t c = 0; c < n_caches; c++) {
         if (!caches[c]) return fail(FWGPU_ERR_INVALID, "set_caches: NULL cache");
         if (caches[c]->owner != b->owner) return fail(FWGPU_ERR_INVALID, "set_caches: a cache belongs to another regressor");
+        if (cache_is_stale(b->owner, caches[c])) return fail(FWGPU_ERR_INVALID, std::string("set_caches: ") + kStaleCache);
     }
     for (uint32_t i = 0; i < b->n; i++)
         if (cache_of_example[i] >= n_caches) return fail(FWGPU_ERR_INVALID, "set_caches: cache_of_example holds an index >= n_caches");
@@ -1832,7 +1896,24 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
     b->req_T = reinterpret_cast<const float *const *>(dev);
     b->req_base = reinterpret_cast<float *>(static_cast<unsigned char *>(dev) + table);
     b->req_of = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(dev) + table + base);
+    b->req_of_n = b->n;
+    b->req_single = false;
     b->req_caches.assign(caches, caches + n_caches);
+    return FWGPU_OK;
+}
+
+// ONE cache for every example of an entry batch of a packed regressor: the set of one.  The table of the call before is kept where it still says the
+// same (the single-example calls attach the same cache request after request).
+static int requests_attach_single(fwgpu_batch *b, const fwgpu_block_cache *c) {
+    if (b->req_dev && b->req_single && b->req_of_n >= b->n && b->req_single_T == c->d_T) {
+        b->req_caches.assign(1, c);
+        return FWGPU_OK;
+    }
+    const std::vector<uint32_t> zeros(std::max<uint32_t>(b->n, 1), 0u);
+    const int rc = fwgpu_batch_set_caches(b, &c, 1, zeros.data());
+    if (rc != FWGPU_OK) return rc;
+    b->req_single = true;
+    b->req_single_T = c->d_T;
     return FWGPU_OK;
 }
 
@@ -1937,6 +2018,59 @@ int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes) {
     if (!r || !storage || !table_bytes) return fail(FWGPU_ERR_INVALID, "NULL argument");
     *storage = r->packed() ? FWGPU_FFM_F16_BUCKETS : FWGPU_FFM_F32;
     *table_bytes = r->packed() ? r->ffm_q_bytes : (r->ffm_len ? (r->ffm_len + 64) * sizeof(float) : 0);
+    return FWGPU_OK;
+}
+
+int fwgpu_packed_enable_caches(fwgpu_regressor *r) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (!r->packed()) return fail(FWGPU_ERR_INVALID, "packed_enable_caches: the regressor's FFM weights are f32: its context caches need no switch");
+    r->packed_caches = true;
+    return FWGPU_OK;
+}
+
+int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *weights_epoch) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (enabled) *enabled = r->packed_caches ? 1 : 0;
+    if (weights_epoch) *weights_epoch = r->weights_epoch;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_block_cache_read(const fwgpu_block_cache *c, float *T, float *dcf, uint32_t *cnt, uint64_t *epoch) {
+    if (!c || !c->owner) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    const fwgpu_regressor *r = c->owner;
+    const size_t F = r->cfg.ffm_k ? r->cfg.ffm_num_fields : 0, R = F * r->cfg.ffm_k;
+    FWGPU_HIP(hipSetDevice(r->device));
+    FWGPU_HIP(hipDeviceSynchronize());
+    if (T && F) FWGPU_HIP(hipMemcpy(T, c->d_T, F * R * sizeof(float), hipMemcpyDeviceToHost));
+    if (dcf && F) FWGPU_HIP(hipMemcpy(dcf, c->d_dcf, F * sizeof(float), hipMemcpyDeviceToHost));
+    if (cnt && F) FWGPU_HIP(hipMemcpy(cnt, c->d_cnt, F * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (epoch) *epoch = c->epoch;
+    return FWGPU_OK;
+}
+
+int fwgpu_debug_requests_time(fwgpu_regressor *r, fwgpu_batch *b, int rows, uint32_t reps, float *ms_per_launch) {
+    if (!r || !b || !ms_per_launch || reps == 0) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (b->owner != r) return fail(FWGPU_ERR_INVALID, "batch belongs to another regressor");
+    if (b->req_caches.empty() || b->n == 0) return fail(FWGPU_ERR_INVALID, "debug_requests_time: the batch has no cache set attached");
+    if (rows != 0 && rows != 4 && rows != 8) return fail(FWGPU_ERR_INVALID, "debug_requests_time: rows is 0 (the default), 4 or 8");
+    if (rows && !r->packed()) return fail(FWGPU_ERR_INVALID, "debug_requests_time: an f32 table runs its own depth (rows = 0)");
+    FWGPU_HIP(hipSetDevice(r->device));
+    int rc = run_batch_requests(r, b, 0, 0, rows);  // (warm: the code object, the LDS attribute)
+    if (rc) return rc;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    FWGPU_HIP(hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], 0);
+    for (uint32_t i = 0; i < reps && e == hipSuccess && rc == FWGPU_OK; i++) rc = run_batch_requests(r, b, 0, 0, rows);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    if (ev[1]) (void)hipEventDestroy(ev[1]);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("debug_requests_time: ") + hipGetErrorString(e));
+    *ms_per_launch = ms / (float)reps;
     return FWGPU_OK;
 }
 
@@ -2381,6 +2515,7 @@ int fwgpu_pack_regressor(fwgpu_regressor *src, fwgpu_regressor **out) {
     }
     dst->q_increment = inc;
     dst->q_min = mn;
+    if (!own) dst->weights_epoch++;  // (refreshed in place: the caches set up before hold sums of weights that no longer exist)
     *out = dst;
     return FWGPU_OK;
 }

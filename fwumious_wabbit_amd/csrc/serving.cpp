@@ -13,7 +13,12 @@
 // for those.  Models with a deep head are served through the cache like any other (block_neural.rs:355, block_misc.rs:847, block_relu.rs:123: every block
 // behind the FFM block inherits forward_with_cache): the cache also keeps how many features it holds per field, which is what the head's input diagonal
 // needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (regressor.cpp run_batch_head_predict), a smaller one
-// the per-example kernel.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result.
+// the per-example kernel.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
+// unless the command also holds --packed_context_cache: the model's regressor then gets fwgpu_packed_enable_caches, fw_setup_cache builds the
+// device cache from the packed table (no record cover: every cached call takes the ENTRY route), and fw_predict_with_cache,
+// fwgpu_predictor_predict_batch(with_cache) and fwgpu_predictor_predict_requests score the filtered candidate against it on the requests kernels.
+// fwgpu_predictor_apply_diff makes every such cache stale (the regressor's weights epoch); a predictor rebuilds its cache from the context's entries
+// it keeps before its next cached call, under the model's mutex.
 //
 // fwgpu_predictor_predict_text takes a request as one text, a candidate per line, and keeps the host out of the scan: the device parser
 // (textparse.hip, candidate mode) turns every line that starts with '|' into the candidate-only record fwgpu_parser_parse_candidate defines,
@@ -134,6 +139,8 @@ struct FfiPredictor {
     std::vector<uint32_t> record;
     std::vector<fwgpu_lr_entry> lr;
     std::vector<fwgpu_ffm_entry> ffm;
+    std::vector<fwgpu_lr_entry> ctx_lr;    // --packed_context_cache: the context's entries as fw_setup_cache translated them: what a stale cache
+    std::vector<fwgpu_ffm_entry> ctx_ffm;  // is rebuilt from (lr / ffm above are scratch of every request)
     uint64_t text_lines = 0, text_host_lines = 0;  // fwgpu_predictor_last_text_route
     int text_fell_back = 0;
     ~FfiPredictor() {
@@ -146,6 +153,14 @@ struct FfiPredictor {
 namespace {
 
 constexpr float kEofErrorCode = -1.0f, kExceptionErrorCode = -1.0f;  // lib.rs:47-48
+
+// --packed_context_cache, under the model's mutex: a cache set up before the last hot patch (fwgpu_predictor_apply_diff) is rebuilt from the
+// context's entries, so that no cached call is served from -- or refused for -- sums of weights that no longer exist
+int refresh_stale_cache(FfiPredictor *p) {
+    SharedModel &m = *p->model;
+    if (!p->cache || !m.re->packed() || p->cache->epoch == m.re->weights_epoch) return FWGPU_OK;
+    return fwgpu_setup_cache(m.re, p->ctx_lr.data(), (uint32_t)p->ctx_lr.size(), p->ctx_ffm.data(), (uint32_t)p->ctx_ffm.size(), &p->cache);
+}
 
 // parse -> translate -> predict (lib.rs:70-86).  The record goes to the device as it is (one small copy) and is translated
 // in the example kernel's stage phase, like every other record batch; fwgpu_predictor_predict_batch is the same path with n > 1.
@@ -171,6 +186,7 @@ float predict_line(FfiPredictor *p, const char *prefix, size_t prefix_len, const
     if (prefix && p->cache) {  // predict_with_cache (lib.rs:88-108): translate, then only the uncached features are gathered
         float label, imp, out = 0.0f;
         if (translate_record(&m.tr, p->record.data(), n_words, p->lr, p->ffm, &label, &imp) != FWGPU_OK) return kExceptionErrorCode;
+        if (refresh_stale_cache(p) != FWGPU_OK) return kExceptionErrorCode;
         if (fwgpu_predict_with_cache(m.re, p->cache, p->lr.data(), (uint32_t)p->lr.size(), p->ffm.data(), (uint32_t)p->ffm.size(), &out) != FWGPU_OK)
             return kExceptionErrorCode;
         return out;
@@ -220,10 +236,15 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         if (words[i] == "-i" || words[i] == "--initial_regressor") weights = words[i + 1];
         if (words[i] == "--device") device = std::atoi(words[i + 1].c_str());  // ours: which GPU serves
     }
-    bool packed = false;
+    bool packed = false, packed_caches = false;
     for (const auto &w : words) {
         if (w.rfind("--initial_regressor=", 0) == 0) weights = w.substr(std::strlen("--initial_regressor="));
         if (w == "--packed_weights") packed = true;  // ours: the FFM weights stay f16 buckets on the device (fwgpu_model_load_packed)
+        if (w == "--packed_context_cache") packed_caches = true;  // ours: ... and context caches are built from them (fwgpu_packed_enable_caches)
+    }
+    if (packed_caches && !packed) {
+        set_error("--packed_context_cache is valid only together with --packed_weights (an f32 predictor keeps its context cache without it)");
+        return nullptr;
     }
     if (weights.empty()) {
         set_error("Cannot resolve input weights file name");  // the reference panics here (lib.rs:164-167)
@@ -233,6 +254,7 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
     if ((packed ? fwgpu_model_load_packed(weights.c_str(), device, &model->vw, &model->mi, &model->re)
                 : fwgpu_model_load(weights.c_str(), device, /*immutable=*/1, &model->vw, &model->mi, &model->re)) != FWGPU_OK)
         return nullptr;
+    if (packed_caches && fwgpu_packed_enable_caches(model->re) != FWGPU_OK) return nullptr;
     if (fwgpu_mi_configs(model->mi, device, nullptr, &model->tr, nullptr) != FWGPU_OK) return nullptr;
     auto p = std::make_unique<FfiPredictor>();
     p->model = model;
@@ -272,8 +294,15 @@ float fw_setup_cache(FfiPredictor *ptr, const char *input_buffer) {  // lib.rs:2
     ptr->prefix = nullptr;
     if (fwgpu_parse_prefix_create(ptr->parser, ptr->cached_text.data(), ptr->cached_text.size(), &ptr->prefix) != FWGPU_OK) return kExceptionErrorCode;
     SharedModel &m = *ptr->model;
-    // (a packed regressor keeps no device-side context cache: the whole context + candidate record is scored)
-    if (m.re->cfg.ffm_k != 0 && !m.re->packed()) {
+    // (a packed regressor keeps no device-side context cache: the whole context + candidate record is scored -- unless --packed_context_cache)
+    if (m.re->cfg.ffm_k != 0 && m.re->packed() && m.re->packed_caches) {
+        // the cache from the packed table; no record cover (record batches with a cache are not served on packed weights): delta_ok stays false
+        float label, imp;
+        std::lock_guard<std::mutex> g(m.mu);
+        if (translate_record(&m.tr, ptr->record.data(), n_words, ptr->ctx_lr, ptr->ctx_ffm, &label, &imp) != FWGPU_OK) return kExceptionErrorCode;
+        if (fwgpu_setup_cache(m.re, ptr->ctx_lr.data(), (uint32_t)ptr->ctx_lr.size(), ptr->ctx_ffm.data(), (uint32_t)ptr->ctx_ffm.size(), &ptr->cache) != FWGPU_OK)
+            return kExceptionErrorCode;
+    } else if (m.re->cfg.ffm_k != 0 && !m.re->packed()) {
         // translate_and_filter(buffer, 0, Some(Primitive)) + Regressor::setup_cache (lib.rs:133-146); every namespace this
         // library accepts is primitive (transformed namespaces are refused when the model is loaded)
         float label, imp;
@@ -310,7 +339,8 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
     }
     const bool cached = with_cache && ptr->cache;  // candidates reduced to the entries the context cache does not cover
     // records + the kernel's own translation, unless a candidate turns out to need the entry route (FWGPU_SERVING_ENTRY_ROUTE=1 forces that one)
-    bool by_record = cached && !std::getenv("FWGPU_SERVING_ENTRY_ROUTE");
+    // (--packed_context_cache: the entry route always -- a packed regressor's cache knows no record)
+    bool by_record = cached && !m.re->packed() && !std::getenv("FWGPU_SERVING_ENTRY_ROUTE");
     // ... and of those records only what the candidate adds to the context's record, which the device already holds
     // (FWGPU_SERVING_MERGED_RECORDS=1: whole context + candidate records instead)
     const bool delta_wanted = ptr->delta_ok && !std::getenv("FWGPU_SERVING_MERGED_RECORDS");
@@ -474,6 +504,7 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
         int rc0 = batch_alloc(m.re, nrec, hb.lr_hash.size(), hb.ffm_hash.size(), &eb);
         if (rc0 != FWGPU_OK) return rc0;
         rc0 = batch_upload(eb, hb, 0);
+        if (rc0 == FWGPU_OK) rc0 = refresh_stale_cache(ptr);
         if (rc0 == FWGPU_OK) rc0 = fwgpu_batch_set_cache(eb, ptr->cache);
         if (rc0 == FWGPU_OK) rc0 = fwgpu_learn_batch(m.re, eb, FWGPU_MODE_HOGWILD, /*update=*/0, nullptr);
         std::vector<float> preds(nrec);
@@ -658,7 +689,8 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
     }
     if (total > 0xffffffffull) return fail(FWGPU_ERR_RANGE, "predict_requests: more than 2^32 - 1 lines");
     SharedModel &m = *predictors[0]->model;
-    if (m.re->packed()) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a --packed_weights predictor keeps no device cache") + kSee);
+    if (m.re->packed() && !m.re->packed_caches)
+        return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a --packed_weights predictor keeps no device cache") + kSee);
     if (m.re->cfg.ffm_k == 0) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a model without an FFM block keeps no device cache") + kSee);
     if (m.re->nn.n_layers) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
     std::vector<const fwgpu_block_cache *> caches;  // the set: every predictor's cache once
@@ -787,6 +819,7 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
     eb->max_lr = max_lr;
     eb->max_ffm = max_ffm;
     eb->aligned4 = aligned4;
+    for (uint32_t r = 0; r < n_requests && rc == FWGPU_OK; r++) rc = refresh_stale_cache(predictors[r]);  // (--packed_context_cache: before the set is attached)
     if (rc == FWGPU_OK) rc = fwgpu_batch_set_caches(eb, caches.data(), (uint32_t)caches.size(), ex_cache.data());
     if (rc == FWGPU_OK) rc = fwgpu_learn_batch(m.re, eb, FWGPU_MODE_HOGWILD, /*update=*/0, nullptr);
     std::vector<float> preds(nrec);
@@ -806,8 +839,9 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *ptr, uint64_t *lines, ui
 }
 
 // The hot patch of a --packed_weights model from a byte diff of two published files (fwgpu_packed_apply_diff), under the model's mutex.  The
-// prototype and every clone_lite copy share the tables, so all of them see it; such predictors keep no device cache, so nothing derived from
-// the weights goes stale.
+// prototype and every clone_lite copy share the tables, so all of them see it.  Plain --packed_weights predictors keep no device cache, so nothing
+// derived from the weights goes stale; with --packed_context_cache the patch bumps the regressor's weights epoch under this mutex, and every
+// predictor of the model rebuilds its cache before its next cached call (refresh_stale_cache).
 int fwgpu_predictor_apply_diff(FfiPredictor *ptr, const uint8_t *diff, uint64_t len) {
     if (!ptr || (len && !diff)) return fail(FWGPU_ERR_INVALID, "NULL argument");
     SharedModel &m = *ptr->model;

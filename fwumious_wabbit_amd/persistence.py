@@ -127,9 +127,12 @@ def load_regressor_without_weights(filename: str):
     return ModelInstanceHandle(mi), VwNamespaceMap(_handle=vw)
 
 
-def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0, packed: bool = False):
+def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0, packed: bool = False, packed_caches: bool = False):
     """persistence.rs:127-174 -> (ModelInstance, VwNamespaceMap, Regressor).  packed: an immutable regressor whose FFM weights stay the
-    quantised file's f16 buckets in device memory (fwgpu_model_load_packed): half the table, predict-only"""
+    quantised file's f16 buckets in device memory (fwgpu_model_load_packed): half the table, predict-only.  packed_caches (with packed only):
+    the regressor also keeps context caches (Regressor.enable_packed_caches)"""
+    if packed_caches and not packed:
+        raise ValueError("packed_caches needs packed=True")
     L = capi.lib()
     vw, mih, r = C.c_void_p(), C.c_void_p(), C.c_void_p()
     if packed:
@@ -139,7 +142,10 @@ def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0,
     h = ModelInstanceHandle(mih)
     mi = h.to_model_instance(device)
     h.close()
-    return mi, VwNamespaceMap(_handle=vw), Regressor.from_handle(mi, r)
+    re = Regressor.from_handle(mi, r)
+    if packed_caches:
+        re.enable_packed_caches()
+    return mi, VwNamespaceMap(_handle=vw), re
 
 
 def hogwild_load(re: Regressor, filename: str):

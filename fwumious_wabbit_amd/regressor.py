@@ -251,6 +251,17 @@ class BlockCache:
         r = np.ascontiguousarray(record, dtype=np.uint32)
         return bool(capi.lib().fwgpu_block_cache_record_ok(self.h, C.byref(translator.c), ptr(r), len(r)))
 
+    def debug_read(self):
+        """(T [F, F * k], dcf [F], cnt [F], epoch): the cache as the device holds it -- the context's field sums (row f: the floats facing field f of
+        every field's sum), self-pair corrections and features per field, and the regressor's weights epoch it was set up at
+        (fwgpu_debug_block_cache_read)"""
+        mi = self.regressor.mi
+        F = len(mi.ffm_fields) if mi.ffm_k else 0
+        T, dcf, cnt = np.zeros((F, F * mi.ffm_k), dtype=np.float32), np.zeros(F, dtype=np.float32), np.zeros(F, dtype=np.uint32)
+        ep = C.c_uint64(0)
+        check(capi.lib().fwgpu_debug_block_cache_read(self.h, ptr(T), ptr(dcf), ptr(cnt), C.byref(ep)))
+        return T, dcf, cnt, ep.value
+
     def close(self):
         if self.h:
             capi.lib().fwgpu_block_cache_free(self.h)
@@ -544,6 +555,25 @@ class Regressor:
         st, nb = C.c_int32(0), C.c_uint64(0)
         check(self.L.fwgpu_ffm_storage(self.h, C.byref(st), C.byref(nb)))
         return st.value, nb.value
+
+    def enable_packed_caches(self):
+        """one-way switch on a packed regressor: setup_cache, predict_with_cache and Batch.set_cache / set_caches on entry batches are accepted
+        and take the requests route on the 16-bit table; a cache set up before a refresh (pack(into=)) or apply_diff is refused as stale until
+        setup_cache on the same handle has refilled it -- fwgpu_packed_enable_caches"""
+        check(self.L.fwgpu_packed_enable_caches(self.h))
+
+    def packed_caches_state(self):
+        """(enabled, weights epoch) -- fwgpu_packed_caches_state"""
+        on, ep = C.c_int32(0), C.c_uint64(0)
+        check(self.L.fwgpu_packed_caches_state(self.h, C.byref(on), C.byref(ep)))
+        return bool(on.value), ep.value
+
+    def debug_requests_time(self, batch, rows=0, reps=20) -> float:
+        """milliseconds per launch of the requests route of a batch with a set attached, by device events; rows: the packed predict kernel's rows
+        in flight (4 or 8; 0 = the default) -- fwgpu_debug_requests_time"""
+        ms = C.c_float(0)
+        check(self.L.fwgpu_debug_requests_time(self.h, batch.h, rows, reps, C.byref(ms)))
+        return ms.value
 
     def quantize_ffm_table(self) -> bytes:
         """the FFM weights as the inference file's quantised block (8-byte header {increment, min} + one f16 bucket per weight), made on the

@@ -7,7 +7,12 @@
  *                                                         loaded as an immutable regressor (persistence.rs:127-174);
  *                                                         `--device N` (ours) picks the GPU; `--packed_weights` (ours) keeps
  *                                                         the FFM weights as the quantised file's f16 buckets on the device
- *                                                         (fwgpu_model_load_packed: half the table, same calls).  NULL +
+ *                                                         (fwgpu_model_load_packed: half the table, same calls);
+ *                                                         `--packed_context_cache` (ours, only with --packed_weights, else
+ *                                                         an error) lets such a predictor keep device context caches
+ *                                                         (fwgpu_packed_enable_caches): fw_setup_cache builds one from the
+ *                                                         packed table, the cached calls below and
+ *                                                         fwgpu_predictor_predict_requests score filtered candidates.  NULL +
  *                                                         fwgpu_last_error() on failure (the reference panics).
  *   lib.rs:187-205  clone_lite(prototype)                 cheap per-thread copy sharing the weights
  *   lib.rs:207-212  fw_predict(ptr, vw_text)              -> prediction, or -1.0 for EOF / a line that does not parse
@@ -52,7 +57,7 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint
  * gives no record.  Every line is parsed behind its predictor's context, translated and filtered by that predictor's cache on the
  * host's worker threads; one entry batch with a cache per example follows (fwgpu_batch_set_caches), whose kernel's work per candidate
  * follows the candidate's own features.  FWGPU_ERR_INVALID, pointing to fwgpu_predictor_predict_batch: predictors of different
- * models, a predictor without a device cache (no fw_setup_cache yet, --packed_weights, a model without an FFM block), a model with
+ * models, a predictor without a device cache (no fw_setup_cache yet, --packed_weights without --packed_context_cache, a model without an FFM block), a model with
  * a deep head.  Concurrent callers are not coalesced: each call is one launch under the model's mutex. */
 int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs,
                                      const uint32_t *n_inputs, float *const *out);
@@ -60,7 +65,9 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
 /* Not in the reference's FFI (its weight_patcher rewrites the file): patches a --packed_weights model in place from the bare byte-diff stream
  * of the file it was loaded from and the next published file (include/fwgpu.h: fwgpu_image_diff, fwgpu_diff_bytes; fwgpu_packed_apply_diff
  * states the refusals).  Runs under the model's mutex; the prototype and every clone_lite copy share the tables and see the patch.
- * Predictors without --packed_weights are FWGPU_ERR_INVALID.  A refused or malformed stream leaves the model as it was. */
+ * Predictors without --packed_weights are FWGPU_ERR_INVALID.  A refused or malformed stream leaves the model as it was.
+ * With --packed_context_cache the patch makes every context cache of the model stale (the regressor's weights epoch); each predictor, clones
+ * included, rebuilds its cache from the context's entries it keeps before its next cached call, under the same mutex. */
 int fwgpu_predictor_apply_diff(FfiPredictor *p, const uint8_t *diff, uint64_t len);
 
 #ifdef __cplusplus

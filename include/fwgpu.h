@@ -129,7 +129,7 @@ int fwgpu_predict(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_lr, c
  * block behind the FFM block inherits forward_with_cache, block_neural.rs:355): the cache also keeps how many features it holds per
  * field, and the head's input diagonal of a field with c cached and n gathered features is what an uncached launch computes for
  * c == 0, exactly 0 for c + n <= 1, and 0.5 (|field sum|^2 - sum of the features' own squares) otherwise.  A second
- * fwgpu_setup_cache on the same handle refreshes sums and counts.  Packed regressors: refused.
+ * fwgpu_setup_cache on the same handle refreshes sums and counts.  Packed regressors: refused, unless fwgpu_packed_enable_caches was called.
  * fwgpu_block_cache_filter: the FFM entries forward_with_cache still gathers (what an entry batch used with
  * fwgpu_batch_set_cache: must hold); predict-only launches of that batch then start every example from the cache. */
 typedef struct fwgpu_block_cache fwgpu_block_cache;
@@ -231,7 +231,7 @@ int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *cache);
  * next launch.  Like every change of a batch's contents, the call must not overlap a launch of the batch that is still in flight.
  * n_caches == 0 detaches; fwgpu_batch_set_cache on the same batch replaces the set, and the other way round.
  * FWGPU_ERR_INVALID, the batch left as it was: a record batch, an index >= n_caches, a cache of another regressor, a regressor with
- * a deep head or packed weights, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
+ * a deep head or packed weights (without fwgpu_packed_enable_caches), a stale cache of a packed regressor, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
  * whose min(fields, largest FFM entry count of an example) * F * k floats exceed the 160 KiB LDS returns FWGPU_ERR_RANGE. */
 int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches,
                            const uint32_t *cache_of_example /* [examples of b] */);
@@ -599,6 +599,7 @@ int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 #define FWGPU_KERNEL_RESIDENT 2 /* register-resident kernel (rows of up to 256 floats, or up to 512 where 256 % k == 0) */
 #define FWGPU_KERNEL_PACKED 3   /* ... its predict-only instantiation on a packed table */
 #define FWGPU_KERNEL_REQUESTS 4 /* the requests kernels (FWGPU_ROUTE_REQUESTS): [1] = ceil(R / 256), [6] = threads per workgroup, [7] = LDS bytes, [2]..[5] = 0 */
+#define FWGPU_KERNEL_PACKED_REQUESTS 5 /* ... their instantiation on a packed table (fwgpu_packed_enable_caches); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_LAUNCH_INFO_LEN 8
 int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
@@ -839,7 +840,7 @@ int fwgpu_model_load(const char *path, int device, int immutable, fwgpu_vwmap **
  * fwgpu_table_read / fwgpu_table_checksum of FWGPU_TABLE_FFM_W (the dequantised values).  Everything that would write or
  * train -- update != 0, fwgpu_learn_batch_sync, fwgpu_table_write / fill / device_ptr on the FFM tables, fwgpu_read_weights,
  * fwgpu_write_weights, fwgpu_model_save, fwgpu_trainer_create, fwgpu_dist_*, hogwild_load into it -- and fwgpu_setup_cache
- * return FWGPU_ERR_INVALID and leave it usable.
+ * (unless fwgpu_packed_enable_caches was called, below) return FWGPU_ERR_INVALID and leave it usable.
  * Refused here with FWGPU_ERR_INVALID: models with a deep head, models without an FFM block, ffm_k % 4 != 0, rows
  * (ffm_k x fields) of more than 256 weights unless ffm_k divides 256 and the row has at most 512.  Refused at the launch:
  * entry batches with an FFM hash that is not a multiple of 4 (raw entries that did not pass fwgpu_ffm_hash_mask), examples
@@ -848,6 +849,30 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw, fwgp
 /* How the FFM weight table lives on the device, and the bytes it occupies there */
 enum { FWGPU_FFM_F32 = 0, FWGPU_FFM_F16_BUCKETS = 1 };
 int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes);
+/* ---- context caches on a packed regressor (opt-in).  fwgpu_packed_enable_caches is a ONE-WAY switch on a packed regressor (made by
+ * fwgpu_model_load_packed or fwgpu_pack_regressor, whose refresh in place keeps it); an f32 regressor is FWGPU_ERR_INVALID.  Without it every
+ * call answers as above.  With it, on that regressor:
+ *   fwgpu_setup_cache          builds the cache with the packed build kernel (csrc/requests.hip): T, dcf and the counts in the layout and summation
+ *                              order an f32 regressor's cache has, from the values the buckets stand for
+ *   fwgpu_block_cache_filter   as ever
+ *   fwgpu_batch_set_cache      on an ENTRY batch: the set of one; fwgpu_batch_set_caches: a cache per example.  A predict-only launch of such a
+ *                              batch takes FWGPU_ROUTE_REQUESTS with the kernel family FWGPU_KERNEL_PACKED_REQUESTS; update != 0, an oversize
+ *                              example, a hash off the 4-bucket boundary (FWGPU_ERR_INVALID) and the LDS range (FWGPU_ERR_RANGE) as on f32 tables
+ *   fwgpu_predict_with_cache   the same route for one example
+ * Record batches with a cache stay refused: fwgpu_block_cache_cover_record and fwgpu_batch_set_cache on a record batch are FWGPU_ERR_INVALID
+ * and name the entry route.
+ * STALENESS.  The regressor carries a weights epoch, bumped by fwgpu_packed_apply_diff (when it applies an entry) and by fwgpu_pack_regressor's
+ * refresh in place.  A cache records the epoch at fwgpu_setup_cache.  Attaching a cache of an older epoch (fwgpu_batch_set_cache(s)), launching a
+ * batch that holds one, and fwgpu_predict_with_cache with one are FWGPU_ERR_INVALID ("stale"), the batch left as it was: nothing is served from
+ * sums of weights that no longer exist.  fwgpu_setup_cache on the same handle refills the cache at the current epoch. */
+int fwgpu_packed_enable_caches(fwgpu_regressor *r);
+int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *weights_epoch); /* either output may be NULL */
+/* debug: a cache's contents as the device holds them -- T [F * F * k], dcf [F], cnt [F], the epoch it was set up at (each may be NULL).  Waits for the device. */
+int fwgpu_debug_block_cache_read(const fwgpu_block_cache *cache, float *T, float *dcf, uint32_t *cnt, uint64_t *epoch);
+/* debug (scripts/bench_serving_packed_requests.py): milliseconds per launch, by device events over `reps` launches on the null stream, of the
+ * requests route of a batch with a set attached (base kernel + predict kernel).  rows: the packed predict kernel's rows in flight per lane, 4 or 8,
+ * 0 = the default (the only value an f32 regressor takes). */
+int fwgpu_debug_requests_time(fwgpu_regressor *r, fwgpu_batch *b, int rows, uint32_t reps, float *ms_per_launch);
 /* ---- quantising on the device: train -> publish -> serve without the training blob crossing to the host
  * The reference's quantiser (quantization.rs:18-80) as HIP kernels (csrc/quantize.hip): a statistics pass (min, max, "a weight is not finite")
  * over exactly the table's weights, the header {increment, min} formed on the host from the two reduced floats by the host quantiser's own
