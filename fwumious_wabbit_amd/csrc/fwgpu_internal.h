@@ -677,6 +677,8 @@ struct HostBatch {  // SoA staging of a CSR batch on the host
     uint32_t max_lr = 0, max_ffm = 0;
     bool aligned4 = true;
     void clear();
+    // a new example: entries [f0, f1) / [l0, l1) (indices into src's arrays) of src's example e, with its label and importance
+    void append_slice(const HostBatch &src, uint32_t e, uint32_t f0, uint32_t f1, uint32_t l0, uint32_t l1);
     uint32_t size() const { return (uint32_t)label.size(); }
 };
 int batch_alloc(fwgpu_regressor *r, uint32_t n, uint64_t n_lr, uint64_t n_ffm, fwgpu_batch **out, bool host_mapped = false);
@@ -756,7 +758,6 @@ int record_batch_upload(fwgpu_batch *b, const fwgpu_translator_config *t, const 
 uint32_t lr_hash_mask(uint32_t bit_precision);
 uint32_t ffm_hash_mask(uint32_t ffm_bits, uint32_t ffm_k);
 void lut_init(float *lut, float learning_rate, float power_t, float init_acc);
-KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int update);
 int refuse_packed(const fwgpu_regressor *r, const char *what);  // FWGPU_ERR_INVALID on a packed regressor, FWGPU_OK otherwise
 int create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out);
 // ---- quantising a live regressor's FFM weights (model_file.cpp: the host quantiser; regressor.cpp: the device route and its callers)
@@ -794,5 +795,4 @@ int split_update(fwgpu_regressor *r, fwgpu_batch *b, fwgpu_split *sp, int mode, 
 // mini-batched deep head on the records' x (head.hip): forward, sigmoid, backward, one AdaGrad step per dense weight
 int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, float *d_pred, bool update, hipStream_t stream);
 void head_scratch_free(fwgpu_regressor *r);
-uint32_t pick_grid(const fwgpu_regressor *r, const KernelParams &p, int mode, uint32_t threads);
 }  // namespace fwgpu

@@ -2769,7 +2769,7 @@ __device__ __forceinline__ uint32_t split_lead(const Lds &s, uint32_t lo) {
 #define FW_PIPE_DEPTH 3
 #endif
 // Rows of a wave's range BEYOND the FW_MAXR_WIN register-kept ones whose gather-time w is parked in LDS (Lds::keep) instead of being re-read by the
-// update phase: at most this many per wave; the host grants as many as leave two workgroups on a CU (regressor.cpp prepare_launch, KernelParams::lds_keep).
+// update phase: at most this many per wave; the host grants as many as leave two workgroups on a CU (launch.cpp plan_launch, KernelParams::lds_keep).
 // Config C: 55 KB + 3 x 7.7 KB per workgroup -> 3 rows, 23 of ~25 rows per wave written back as w_gather - step; +0.7 % examples/s and 0.002 of hold-out
 // loss after 10 M examples; a fourth slot that stays empty costs 0.15 %.
 #ifndef FW_LDS_KEEP_MAX  // rows per wave parked in LDS, at most (profiles/r04_parked_rows_ab.txt)
@@ -3676,7 +3676,7 @@ static hipError_t launch_resident(const KernelParams &p, int optimizer, bool coh
 static bool uses_resident_kernel(const KernelParams &p, uint32_t threads) {
     // rows of up to 256 floats (one 16-byte chunk per lane) or up to 512 (two chunks; a field slot must not straddle the chunks)
     const bool fits = p.R <= 64 * 4 || (p.R <= 64 * 4 * 2 && p.k != 0 && 256 % p.k == 0);
-    // a deep head: read-only launches that only form its input (emit_x), and -- nn_v2, chosen by prepare_launch where two workgroups fit a CU -- config E's concurrent updating launches
+    // a deep head: read-only launches that only form its input (emit_x), and -- nn_v2, chosen by plan_launch where two workgroups fit a CU -- config E's concurrent updating launches
     const bool head_ok = p.nn.n_layers == 0 || (p.emit_x && !p.update) || (p.nn_v2 && p.update && p.R > 64 * 4);
     return p.k % 4 == 0 && p.aligned4 && fits && p.kernel_version != 1 && head_ok && threads <= ((p.nn_v2 && p.update) ? (FW_NN_THREADS > FW_LB_THREADS ? FW_NN_THREADS : FW_LB_THREADS) : FW_LB_THREADS);
 }
@@ -3695,7 +3695,7 @@ void resolve_row_mode(KernelParams &p, uint32_t threads) {
     p.prefetch = (p.prefetch && p.records && p.update && uses_resident_kernel(p, threads)) ? 1 : 0;
     p.tr_lds = (p.records && uses_resident_kernel(p, threads)) ? 1 : 0;  // the v2 kernel reads the translator's tables from an LDS copy
     // The v2 kernel's single-chunk updating instantiations keep the LUT in LDS as a compile-time fact (kLdsLut): settled HERE, so that the host's
-    // LDS size -- the occupancy choice and the 160 KiB check of prepare_launch -- is the size the launch really uses (debug option 1 does not apply to them).
+    // LDS size -- the occupancy choice and the 160 KiB check of plan_launch -- is the size the launch really uses (debug option 1 does not apply to them).
     p.lut_lds_forced = (uses_resident_kernel(p, threads) && p.R <= 64 * 4 && p.update) ? 1 : 0;
     // The entries' own slots (Lds::selfw: every row's w[f_i * k ..] as the gather read it) are read by the update and by the generic kernel's head only.  Read-only launches of the
     // v2 kernel do without them -- and so do its CONCURRENT whole-line updates (update_rows_win): the row the update has just re-read holds the same slot, as fresh as the rest of

@@ -12,7 +12,7 @@
 // equal to a cached one, takes the entry route (host translation + fwgpu_block_cache_filter), which is the reference's rule
 // for those.  Models with a deep head are served through the cache like any other (block_neural.rs:355, block_misc.rs:847, block_relu.rs:123: every block
 // behind the FFM block inherits forward_with_cache): the cache also keeps how many features it holds per field, which is what the head's input diagonal
-// needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (regressor.cpp run_batch_head_predict), a smaller one
+// needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (launch.cpp run_batch_head_predict), a smaller one
 // the per-example kernel.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
 // unless the command also holds --packed_context_cache: the model's regressor then gets fwgpu_packed_enable_caches, fw_setup_cache builds the
 // device cache from the packed table (no record cover: every cached call takes the ENTRY route), and fw_predict_with_cache,

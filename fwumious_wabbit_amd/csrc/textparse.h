@@ -26,7 +26,7 @@ struct TextNsTable {
 __host__ __device__ inline bool ns_ok(const TextNsTable &t) { return t.slots && t.num_namespaces <= kTextMaxNamespaces; }
 
 // The translator as the status pass needs it for a line's entry counts (translate.cpp count_record) and for the cache's record rule
-// (regressor.cpp block_cache_record_ok): combos as CSR over namespaces, the (field, namespace) pairs in field order.  combo_off == NULL: no counts.
+// (context_cache.cpp block_cache_record_ok): combos as CSR over namespaces, the (field, namespace) pairs in field order.  combo_off == NULL: no counts.
 struct TextTranslator {
     const uint32_t *combo_off;  // [n_combos + 1]
     const uint32_t *combo_ns;

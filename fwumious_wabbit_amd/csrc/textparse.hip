@@ -17,7 +17,7 @@
 // '|' opens a namespace of its own, so the scan does not depend on the context and its record is the stand-alone one with the context's
 // words 1 and 2 and NO_FEATURES in every slot whose merged form equals the context's slot word -- fwgpu_parser_parse_candidate's
 // candidate-only record (parser.cpp).  With a translator (TextParseArgs::tr) the status pass also counts the line's LR and FFM entries
-// (translate.cpp count_record) and, in candidate mode, decides the cache's record rule (regressor.cpp block_cache_record_ok) exactly.
+// (translate.cpp count_record) and, in candidate mode, decides the cache's record rule (context_cache.cpp block_cache_record_ok) exactly.
 //
 // Micro-batch plan (training from text, textparse.h): from a piece's status array alone, a rocPRIM select lists the NEEDS_HOST lines, a rocPRIM scan
 // places every taken line's record, and one workgroup per launch window sums what the host would otherwise count from the records.

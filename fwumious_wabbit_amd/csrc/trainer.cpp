@@ -125,7 +125,7 @@ static int stage_slot(fwgpu_trainer *tr, int c, uint32_t n) {
     // compute stream only waits for THIS buffer's copy (one stream for both cost the copy's 0.6 ms per 16 384 examples: 4.0 -> 4.6 M ex/s).
     int rc = record_batch_upload(b, &tr->t, tr->rec[c], tr->off[c].data(), n, tr->copy_stream, &tr->stats[c]);
     if (rc) return rc;
-    // (a record that translates to more entries than a workgroup stages: the micro-batch is walked example by example, regressor.cpp learn_one_chunked)
+    // (a record that translates to more entries than a workgroup stages: the micro-batch is walked example by example, launch.cpp learn_one_chunked)
     if ((rc = record_batch_host_copy_if_oversize(r, &tr->t, b, tr->rec[c], tr->off[c].data(), n))) return rc;
     FWGPU_HIP(hipEventRecord(tr->uploaded[c], tr->copy_stream));
     FWGPU_HIP(hipStreamWaitEvent(tr->stream, tr->uploaded[c], 0));

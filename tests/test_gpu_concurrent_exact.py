@@ -187,7 +187,7 @@ def test_config_c_kernel(case):
 
 
 # ------------------------------------------------------------------ (b) the 128-thread small-example shape
-# prepare_launch takes the 128-thread, two-waves-per-example launch when max_ffm <= 32 && max_lr <= 64 (both rounded up to a multiple of 4):
+# plan_launch (launch.cpp) takes the 128-thread, two-waves-per-example launch when max_ffm <= 32 && max_lr <= 64 (both rounded up to a multiple of 4):
 B_CASES = {
     "ffm32": dict(first_ffm=32),  # 32 FFM features in the largest example: the 128-thread launch
     "ffm33": dict(first_ffm=33),  # 33 (-> 36): the 512-thread launch

@@ -1,4 +1,4 @@
-"""Deep-head models served through the context cache (regressor.cpp fwgpu_setup_cache / fwgpu_predict_with_cache / fwgpu_batch_set_cache, serving.cpp).
+"""Deep-head models served through the context cache (context_cache.cpp fwgpu_setup_cache / fwgpu_predict_with_cache / fwgpu_batch_set_cache, serving.cpp).
 
 The cache keeps, next to the context's field sums T and self-pair corrections dcf, how many features it holds per field.  With c the cached and n the
 gathered count of a field, the head's input diagonal is: c == 0 -- what an uncached launch computes; c + n <= 1 -- exactly 0; otherwise

@@ -1,4 +1,4 @@
-"""The batched deep-head predict route (regressor.cpp run_batch_head_predict: the example kernel's emit_x epilogue -> head_step(update = false) ->
+"""The batched deep-head predict route (launch.cpp run_batch_head_predict: the example kernel's emit_x epilogue -> head_step(update = false) ->
 head_final_kernel) per example against the oracle, and its head inputs slot by slot against a float64 restatement (head_ref.py, pinned against the
 oracle on the CPU by test_head_predict_ref_cpu.py).
 

@@ -951,7 +951,7 @@ def test_very_large_examples():
     assert np.all(np.isfinite(b.predictions()))
     b.close()
     re.close()
-    # more than a workgroup stages (4096 entries), or more than the LDS holds (3900 + 3900): the chunked path (regressor.cpp learn_one_chunked), same
+    # more than a workgroup stages (4096 entries), or more than the LDS holds (3900 + 3900): the chunked path (launch.cpp learn_one_chunked), same
     # results as the oracle -- round 3 refused these with FWGPU_ERR_RANGE
     om2, re2 = fwo.Model(ocfg), fw.Regressor(mi)
     for n_ffm, n_lr in ((4100, 1), (3900, 3900), (30, 5000)):
@@ -1051,7 +1051,7 @@ def test_table_placement_search_is_transparent(monkeypatch):
 
 def _chunked_path_parity(n_feat, opt, F=8, k=4, bits=16, ffm_bits=16):
     """The reference takes an example of any size (its gradient cache moves to the heap beyond 170 393 floats, block_ffm.rs:294-312).  The fused
-    kernel stages at most 4096 entries; larger examples go through the synchronous pipeline chunk by chunk (regressor.cpp learn_one_chunked).
+    kernel stages at most 4096 entries; larger examples go through the synchronous pipeline chunk by chunk (launch.cpp learn_one_chunked).
     Against the oracle: predict, three learn calls on three different huge examples -- rows repeated across chunks, rows that overlap rows of
     other chunks, LR hashes repeated across chunks included -- then an ordinary small example, per-call predictions and the final tables."""
     mi, ocfg, _ = make_pair(F, k, bits, ffm_bits, opt, lr=0.01, ffm_lr=0.01)
