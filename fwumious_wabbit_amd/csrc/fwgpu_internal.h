@@ -163,6 +163,7 @@ struct KernelParams {
     int32_t store_policy;               // hogwild launches of the v2 window kernel: how FFM row stores reach memory (kernels.hip "store policy"): 0 = both tables
                                         // device-scope write-through, 1 = weights write-back through the XCD's L2, 2 = both tables write-back
     float acc_hot_theta;                // policy 3: a kept row whose accumulators exceed this is "hot": its accumulator row is stored for one example in
+    float acc_tier[3];                  // policy 4: accumulator levels (8, 16, 32 x the threshold, initial value folded in) beyond which a hot row's adds are thinned one step further each (hot_tiers.h); +inf = tiers off
     int32_t no_kept_rows;               // the large-table kernel without rows kept from the gather (fwgpu_debug_set_option 13 / FWGPU_KEPT_ROWS=0): every row re-read by the update
     float lr_hot_theta;                 // store policy 4 on the LR block: an entry whose accumulator exceeds this is hot (its initial value + the FFM rows' theta)
     int32_t lr_thin;                    // ... on (1) / off (0): FWGPU_LR_THIN, fwgpu_debug_set_option 12
@@ -253,6 +254,7 @@ struct LaunchConfig {
     int32_t nn_v2 = -1;              // debug option 11: deep head of concurrent two-chunk launches on the v2 kernel (-1: FWGPU_NN_V2 or on)
     float acc_hot_theta = -1.0f;     // debug option 9: policies 3 / 4, a row is hot once its accumulators have grown by this much (-1: FWGPU_ACC_HOT_THETA or 0.5)
     int32_t acc_sample_log2 = -1;    // debug option 10: policies 3 / 4, one example in 2^this touches a hot row's accumulators (-1: FWGPU_ACC_SAMPLE_LOG2 or 3)
+    int32_t acc_tiers = -1;          // debug option 15: policy 4, hot rows beyond 8 / 16 / 32 x the threshold are sampled one in 16 / 32 / 64 (hot_tiers.h); 0 = every hot row at the base exponent (-1: FWGPU_ACC_TIERS or FWGPU_ACC_TIERS_DEFAULT)
     int32_t wb_flush_every = -1;     // debug option 6: write-back interval of policies 1 / 2 in examples per workgroup (-1: default, 0: never)
     int32_t lds_keep = -1;           // debug option 8: rows per wave kept in LDS beyond the register-kept ones (-1: as many as leave two workgroups per CU)
     int32_t prefetch = 1;            // debug option 7: next-record prefetch of the v2 kernel (A/B runs)

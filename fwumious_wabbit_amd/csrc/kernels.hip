@@ -28,6 +28,7 @@
 // plain cached loads.
 #include "fwgpu_internal.h"
 #include "fwgpu_device.h"
+#include "hot_tiers.h"
 #include "wave_balance.h"
 #include <cstdlib>
 #include <cstddef>
@@ -51,6 +52,10 @@
 //      hot rows kept 0.15-0.29 of their true sum under policies 0, 1 and 3 alike).  An add cannot lose: what reaches memory is an unbiased estimate of the TRUE sum
 //      of g^2 over all concurrent examples -- what the reference's hogwild threads count (hogwild.rs:89-103: `acc += g*g` on coherent memory, optimizer.rs:147-149)
 //      -- at an m-th of the requests.  It applies to every row of a wave (kept in registers, parked in LDS, re-read), since there is no race to lose.
+//      m is the ROW's own, by its heat (hot_tiers.h; fwgpu_debug_set_option(r, 15, 0) / FWGPU_ACC_TIERS=0: off): 2^acc_sample_log2 up to 8 x the threshold, then one step of
+//      the exponent more beyond each of KernelParams::acc_tier's levels (8, 16, 32 x the threshold: one example in 16, 32, 64).  The add is unbiased whatever m is; what m
+//      costs is the quantum m g^2 set against an accumulator of that size, and from the first level on that is at most a quarter of what m = 8 is at the threshold.
+//      The draw is the same for every tier (a longer mask of the same bits).  The LR block's thinning (lr_update) keeps the base m.
 // A write-back line is visible to the other seven XCDs when it leaves this XCD's L2.  Cold lines leave within microseconds (an XCD's 4 MB L2 turns
 // over every ~16 us at this kernel's write rate); a line that is re-touched before it is evicted -- the head rows of a Zipf field -- would stay
 // dirty for the whole launch, each XCD stepping a private copy.  KernelParams::wb_flush_every bounds that window: every that many examples a
@@ -1531,7 +1536,13 @@ __device__ __forceinline__ void update_rows_win(const KernelParams &p, const Lds
                 const f4 a0 = av[u][c];
                 const bool hot = __ballot(inb && (a0[0] > p.acc_hot_theta || a0[1] > p.acc_hot_theta || a0[2] > p.acc_hot_theta || a0[3] > p.acc_hot_theta)) != 0ull;
                 if (hot) {
-                    const uint32_t m = 1u << p.acc_sample_log2;
+                    uint32_t m = 1u << p.acc_sample_log2;
+                    if (p.store_policy == 4) {  // the unit's own m, by its heat: the rule of the kept rows (hot_tiers.h)
+                        const float amax = inb ? fmaxf(fmaxf(a0[0], a0[1]), fmaxf(a0[2], a0[3])) : -__builtin_inff();
+                        const uint32_t tb = (__ballot(amax > p.acc_tier[0]) != 0ull ? 1u : 0u) + (__ballot(amax > p.acc_tier[1]) != 0ull ? 1u : 0u) +
+                                            (__ballot(amax > p.acc_tier[2]) != 0ull ? 1u : 0u);
+                        m = 1u << hot_row_sample_log2(p.acc_sample_log2, tb);
+                    }
                     const uint32_t draw = ((thin_seed * 2654435761u) ^ (idx[u] * 40503u + (uint32_t)c * 9973u)) >> 9;
                     const bool turn = (draw & (m - 1u)) == 0u;
                     if (p.store_policy == 4) {
@@ -3441,6 +3452,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                     av[j] = OPT != FWGPU_OPT_SGD ? Vec<VEC>::template load<AUX_LA>(make_rsrc(p.ffm_acc + h, ok ? R * 4 : 0), e0 * 4) : Vec<VEC>::zero();
                 };
                 uint32_t add_mask = 0;  // policy 4: the slots whose hot row this example adds its (m-fold) g^2 to
+                uint32_t tier_lo = 0, tier_hi = 0;  // ... and, per slot, the two bits of how many tier levels that row is beyond (hot_tiers.h): its own m
 #pragma unroll
                 for (int sl = 0; sl < NS; ++sl) {
                     const int d_prev = sl < DMAX ? sl : DMAX, d_now = sl + 1 < DMAX ? sl + 1 : DMAX;
@@ -3460,7 +3472,17 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                         if (hot) {
                             const uint32_t m = 1u << p.acc_sample_log2;
                             const uint32_t draw = ((ex * 2654435761u) ^ ((kb_u + (uint32_t)sl) * 40503u + (uint32_t)wave * 9973u)) >> 9;
-                            const bool turn = ok0 && (draw & (m - 1u)) == 0u;
+                            bool turn = ok0 && (draw & (m - 1u)) == 0u;
+                            if (kAtom && turn) {
+                                // Policy 4: the row's OWN m, by its heat (hot_tiers.h).  Every tier's mask extends the base one on the same draw, so only a slot whose
+                                // one-in-m turn came can have its one-in-(2, 4, 8) m turn: the levels are compared for those slots alone.  (No memory operation in here.)
+                                const float amax = fmaxf(fmaxf(a_cur[0], a_cur[1]), fmaxf(a_cur[2], a_cur[3]));
+                                const uint32_t tb = (__ballot(amax > p.acc_tier[0]) != 0ull ? 1u : 0u) + (__ballot(amax > p.acc_tier[1]) != 0ull ? 1u : 0u) +
+                                                    (__ballot(amax > p.acc_tier[2]) != 0ull ? 1u : 0u);
+                                turn = (draw & ((1u << hot_row_sample_log2(p.acc_sample_log2, tb)) - 1u)) == 0u;
+                                tier_lo |= (tb & 1u) << sl;
+                                tier_hi |= (tb >> 1) << sl;
+                            }
                             acc_store = kAtom ? false : turn;
                             acc_add = kAtom && turn;
                             g2_scale = (float)(m - 1u);
@@ -3501,10 +3523,11 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
                     // the entry's own slot as the gather read it, both in LDS.  A plain loop over the few slots whose turn it is: no row is alive in registers here.
                     uint32_t am = __builtin_amdgcn_readfirstlane(add_mask);
                     const uint32_t ksh = p.k_log2;
-                    const float mf = (float)(1u << p.acc_sample_log2);
+                    const uint32_t tl = __builtin_amdgcn_readfirstlane(tier_lo), th = __builtin_amdgcn_readfirstlane(tier_hi);
                     while (am) {
                         const uint32_t sl = (uint32_t)__builtin_ctz(am);
                         am &= am - 1u;
+                        const float mf = (float)(1u << hot_row_sample_log2(p.acc_sample_log2, ((tl >> sl) & 1u) | (((th >> sl) & 1u) << 1)));  // the row's own m
                         const uint32_t i = kb_u + sl;
                         const uint32_t h = __builtin_amdgcn_readfirstlane(s.e_hash[i]);
                         const uint32_t f = __builtin_amdgcn_readfirstlane(s.e_fld[i]) & kFldMask;

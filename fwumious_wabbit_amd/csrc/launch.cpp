@@ -8,10 +8,14 @@
 
 #include <algorithm>
 
+#include "hot_tiers.h"
 #include "launch.h"
 
 #ifndef FWGPU_LR_THIN_DEFAULT  // store policy 4 also on hot LR entries of the large-table path (kernels.hip lr_update; DESIGN 4.2: shipped in round 6)
 #define FWGPU_LR_THIN_DEFAULT 1
+#endif
+#ifndef FWGPU_ACC_TIERS_DEFAULT  // store policy 4: hot rows beyond 8 / 16 / 32 x the threshold sampled one in 16 / 32 / 64 (hot_tiers.h; DESIGN 4.2, profiles/hot_tiers_ab.txt)
+#define FWGPU_ACC_TIERS_DEFAULT 1
 #endif
 namespace fwgpu {
 
@@ -106,6 +110,12 @@ KernelParams make_params(const fwgpu_regressor *r, const fwgpu_batch *b, int upd
         p.acc_hot_theta = theta + initial_acc(r->cfg.optimizer, r->cfg.ffm_init_acc_gradient);
         const int sm = r->launch.acc_sample_log2 >= 0 ? r->launch.acc_sample_log2 : (env_sm ? atoi(env_sm) : 3);
         p.acc_sample_log2 = (uint32_t)std::min(std::max(sm, 0), 6);  // (1u << it in the kernels: one example in 1 .. 64)
+        {   // the levels beyond which a hot row's adds are thinned further, as accumulator values like acc_hot_theta (A/B runs: FWGPU_ACC_TIERS=0, option 15)
+            static const char *env_ti = getenv("FWGPU_ACC_TIERS");
+            const bool tiers = (r->launch.acc_tiers >= 0 ? r->launch.acc_tiers : (env_ti ? atoi(env_ti) : FWGPU_ACC_TIERS_DEFAULT)) != 0;
+            for (uint32_t t = 0; t < kHotTiers; ++t)
+                p.acc_tier[t] = hot_tier_level(theta, initial_acc(r->cfg.optimizer, r->cfg.ffm_init_acc_gradient), t, tiers);
+        }
         static const char *env_kr = getenv("FWGPU_KEPT_ROWS");
         p.no_kept_rows = (r->launch.kept_rows >= 0 ? r->launch.kept_rows == 0 : (env_kr && env_kr[0] == '0')) ? 1 : 0;
         static const char *env_lt = getenv("FWGPU_LR_THIN");

@@ -442,6 +442,10 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value) {
         if (value < -1 || value > 6) return fail(FWGPU_ERR_INVALID, "accumulator sampling option: -1, or 0 .. 6");
         r->launch.acc_sample_log2 = value;
         return FWGPU_OK;
+    case 15:  // policy 4: hot rows beyond 8 / 16 / 32 x the threshold are sampled one step of the exponent further each (hot_tiers.h): 1 on, 0 = every hot row at option 10's exponent, -1 = default
+        if (value < -1 || value > 1) return fail(FWGPU_ERR_INVALID, "hot-row tiers option: -1, 0 or 1");
+        r->launch.acc_tiers = value;
+        return FWGPU_OK;
     case 6:  // write-back interval of policies 1 / 2: a workgroup issues buffer_wbl2 every `value` of its examples (0 never, -1 the build's default)
         if (value < -1 || value > 65536) return fail(FWGPU_ERR_INVALID, "write-back interval option: -1 .. 65536 examples");
         r->launch.wb_flush_every = value;

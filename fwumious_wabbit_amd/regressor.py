@@ -451,11 +451,15 @@ class Regressor:
         check(self.L.fwgpu_debug_set_option(self.h, 5, int(policy)))
         check(self.L.fwgpu_debug_set_option(self.h, 6, int(flush_every)))
 
-    def set_hot_row_sampling(self, theta=-1.0, sample_log2=-1):
-        """store policies 3 / 4 (fwgpu_debug_set_option 9 / 10): a row is hot once its accumulators have grown by more than `theta` (default 0.5;
-        resolution 1/1024); one example in 2^sample_log2 (default 3) then touches its accumulator row, with that many times its g^2"""
+    def set_hot_row_sampling(self, theta=-1.0, sample_log2=-1, tiers=None):
+        """store policies 3 / 4 (fwgpu_debug_set_option 9 / 10 / 15): a row is hot once its accumulators have grown by more than `theta` (default 0.5;
+        resolution 1/1024); one example in 2^sample_log2 (default 3) then touches its accumulator row, with that many times its g^2.
+        `tiers` (policy 4; None: left as it is): 1 = a row beyond 8 / 16 / 32 theta is sampled one in 2^(sample_log2 + 1 / 2 / 3), 64 at the most;
+        0 = every hot row at 2^sample_log2; -1 = the default"""
         check(self.L.fwgpu_debug_set_option(self.h, 9, -1 if theta < 0 else int(round(theta * 1024))))
         check(self.L.fwgpu_debug_set_option(self.h, 10, int(sample_log2)))
+        if tiers is not None:
+            check(self.L.fwgpu_debug_set_option(self.h, 15, int(tiers)))
 
     def set_kept_rows(self, on):
         """HOGWILD launches of the large-table kernel keep 20 + 3 rows per wave from the gather and write them back as w_gather - step (1, default: the faster learner, damped on the rows

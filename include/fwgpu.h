@@ -561,6 +561,8 @@ int fwgpu_debug_set_kernel_version(fwgpu_regressor *r, int version);
  *   policy 1 / 2 a workgroup writes its XCD's dirty L2 lines back every `value` of its examples (0 = only when the launch ends; -1 = the
  *   build's default: 128) -- the bound on how long a popular row can stay private to one XCD (DESIGN.md 4.2,
  *   tests/test_gpu_conservation.py).  SEQUENTIAL launches are exact under every policy.
+ * option 15: store policy 4 thins a hot row's adds by the row's heat: 1 = a row whose accumulators have grown by more than 8 / 16 / 32 times option 9's threshold is touched by
+ *   one example in 2^(option 10's value + 1 / 2 / 3), 64 at the most (csrc/hot_tiers.h); 0 = every hot row at option 10's exponent; -1 = default (FWGPU_ACC_TIERS).
  * option 13: rows the large-table kernel keeps from the gather (20 in registers + 3 in LDS per wave, written back as w_gather - step): 1 (default, -1) = kept; 0 = none, every row is
  *   re-read by the update (14 % slower; without the damping of rows many concurrent examples hold -- on BASELINE configs[2]'s stream the reference's own hold-out curve).
  * option 12: store policy 4 also on hot LR entries of that kernel (the weight stored alone, the accumulator by thinned atomic adds): 1 (default, -1) / 0.
