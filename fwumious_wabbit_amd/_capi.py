@@ -272,6 +272,10 @@ def lib():
         "fwgpu_image_read": [vp, vp, u64],
         "fwgpu_image_diff": [vp, vp, vp, u64, P(u64), P(u64)],
         "fwgpu_packed_apply_diff": [vp, vp, u64, P(u64)],
+        "fwgpu_image_apply_diff": [vp, vp, u64, P(u64)],
+        "fwgpu_debug_diff_decode": [i32, vp, u64, u64, vp, vp, u64, P(u64), P(i32)],
+        "fwgpu_debug_decode_geometry": [P(u32)],
+        "fwgpu_debug_decode_rates": [i32, vp, u64, u64, vp],
         "fwgpu_debug_diff": [i32, vp, vp, u64, u64, u64, vp, u64, P(u64), P(u64)],
         "fwgpu_debug_diff_geometry": [P(u32)],
         "fwgpu_debug_diff_rates": [vp, vp, vp],

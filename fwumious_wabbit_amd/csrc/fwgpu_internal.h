@@ -370,15 +370,69 @@ struct DiffArgs {
 hipError_t launch_diff_size(const DiffArgs &d, hipStream_t stream);
 hipError_t launch_diff_scan(const DiffArgs &d, hipStream_t stream);
 hipError_t launch_diff_emit(const DiffArgs &d, hipStream_t stream);
-struct PatchArgs {  // the scatter of a stream's entries into a packed regressor's tables
-    const unsigned long long *index;  // [n] offsets into the file's weights section, ascending
-    const uint8_t *to;                // [n]
-    unsigned long long n;
-    unsigned long long lr_bytes;      // the section's LR part: byte j -> byte (j / 4) * 8 + j % 4 of `lr`
-    unsigned long long q_at, q_bytes; // the buckets begin at q_at: byte j -> byte j - q_at of `q`
-    uint8_t *lr, *q;
+
+// ---- the reader of such a stream on the device (patch_apply.hip): summary pass, tile scan, apply pass
+constexpr uint32_t kDecThreads = 256;                     // four waves
+constexpr uint32_t kDecSteps = 2;                         // steps of 256 lanes x 16 bytes a workgroup walks
+constexpr uint32_t kDecTileBytes = kDecThreads * 16 * kDecSteps;  // 8 KiB: 2^17 tiles for a 1 GiB stream
+constexpr uint32_t kDecScanThreads = 1024;
+struct DecHyp {      // one tile under one start state (0: the reader expects a varint byte, 1: a `to` byte)
+    uint32_t n_to;      // `to` bytes, which is entries: an entry belongs to the tile that holds its `to` byte
+    uint32_t first_to;  // the first one's position in the tile
+    uint32_t pend;      // bytes behind the last one; the tile's length when it has none
+    uint32_t flags;     // bit 0: the state at the tile's end; bits 8-10: the status of the first faulty entry that is not the tile's first
+    unsigned long long rest_sum;  // saturating sum of the deltas of all entries but the first, up to that fault
 };
-hipError_t launch_patch_scatter(const PatchArgs &p, hipStream_t stream);
+struct DecTile {
+    DecHyp h[2];
+};
+struct DecStart {    // scan -> apply pass
+    unsigned long long base_index;   // the index before the tile's first entry
+    unsigned long long first_delta;  // the first entry's delta: its varint may begin in earlier tiles
+    unsigned long long ordinal;      // entries before the tile
+    uint32_t state, pend;            // the resolved start state; bytes of the first entry in earlier tiles (saturating at 255)
+    uint32_t fault;                  // the first entry's varint: kOk or kVarint
+};
+struct DecResult {
+    unsigned long long entries;
+    uint32_t status;                 // diffstream::Status of the whole stream
+    uint32_t final_state;
+};
+// the pinned staging of a large stream's upload (two buffers and their events): made by the first stream that needs it and kept with the
+// image or regressor that is patched, so that a server patched again and again pays for it once
+struct PatchStaging {
+    uint8_t *pinned = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    PatchStaging() = default;
+    PatchStaging(const PatchStaging &) = delete;
+    PatchStaging &operator=(const PatchStaging &) = delete;
+    ~PatchStaging() {
+        if (pinned) (void)hipHostFree(pinned);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+enum DecTarget : uint32_t { kDecToArrays = 0, kDecToImage = 1, kDecToPacked = 2 };
+struct DecArgs {
+    const uint8_t *stream;           // device, len bytes, 16-byte aligned; nothing beyond len is read
+    unsigned long long len, end;     // end: one past the last index an entry may have
+    unsigned long long n_tiles;
+    DecTile *tiles;                  // [n_tiles]
+    DecStart *starts;                // [n_tiles]
+    DecResult *result;
+    // the apply pass's target map
+    uint32_t target;
+    unsigned long long skip_below;   // image, packed: the file's header bytes; entries below are the host's, index - skip_below is section byte j
+    uint8_t *weights;                // image: the weights section, byte j.  packed: the {w, acc} pair table, LR byte j -> byte (j / 4) * 8 + j % 4
+    unsigned long long lr_bytes;     // packed: the section's LR part; the 8 bytes behind it go to q_header, the rest to buckets
+    uint8_t *buckets, *q_header;
+    unsigned long long *out_index;   // arrays: entry i -> out_index[i], out_to[i] while i < cap
+    uint8_t *out_to;
+    unsigned long long cap;
+};
+hipError_t launch_dec_summary(const DecArgs &d, hipStream_t stream);
+hipError_t launch_dec_scan(const DecArgs &d, hipStream_t stream);
+hipError_t launch_dec_apply(const DecArgs &d, hipStream_t stream);
 
 // ---- progressive / hold-out loss (metrics.hip): one launch scores n predictions against their labels into a window table and two totals
 constexpr uint64_t kMetricsNoLabel = 255;  // parser.rs:28 NO_LABEL, as translate_record turns it into a float
@@ -566,6 +620,7 @@ struct fwgpu_regressor {
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     void *metrics_scratch = nullptr;  // fwgpu_batch_metrics: one set of sums and histograms on the device (metrics.hip)
+    fwgpu::PatchStaging patch_staging;       // fwgpu_packed_apply_diff (patch_apply.hip)
 };
 
 // The inference file fwgpu_model_save_inference would write, split in two (model_file.cpp: capture and load; patch.hip: the diff)
@@ -574,6 +629,7 @@ struct fwgpu_image {
     std::vector<uint8_t> header;  // host: write_header + the u64 element count
     uint8_t *d_weights = nullptr; // device, ONE allocation in file order: LR weights (f32), the FFM block, the dense layers' weights
     uint64_t weights_bytes = 0;
+    fwgpu::PatchStaging patch_staging;   // fwgpu_image_apply_diff (patch_apply.hip)
 };
 
 // device buffers of one synchronous micro-batch (regressor.cpp "split pipeline")

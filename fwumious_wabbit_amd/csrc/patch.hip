@@ -1,5 +1,5 @@
 // The reference's weight_patcher (weight_patcher/src/main.rs) on the device: the byte diff of two inference weights sections that live in
-// device memory, as the stream diff_stream.h states, and the scatter of such a stream into a packed regressor's tables.
+// device memory, as the stream diff_stream.h states.  The reader of such a stream on the device is patch_apply.hip.
 //
 // CONTRACT: the stream is that of the host codec (diff_stream.h encode) on the same bytes, byte for byte.
 //
@@ -275,27 +275,6 @@ hipError_t launch_diff_emit(const DiffArgs &d, hipStream_t stream) {
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void patch_scatter_kernel(PatchArgs p) {
-    const unsigned long long stride = (unsigned long long)gridDim.x * 256;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < p.n; i += stride) {
-        const unsigned long long j = p.index[i];
-        const uint8_t v = p.to[i];
-        // bytes are stored as bytes: two entries of one word may be on different lanes
-        if (j < p.lr_bytes)
-            p.lr[(j >> 2) * 8 + (j & 3)] = v;  // the weight half of the {w, acc} pair
-        else if (j >= p.q_at && j - p.q_at < p.q_bytes)
-            p.q[j - p.q_at] = v;
-    }
-}
-
-hipError_t launch_patch_scatter(const PatchArgs &p, hipStream_t stream) {
-    if (!p.n) return hipSuccess;
-    if (!p.index || !p.to || !p.lr || !p.q) return hipErrorInvalidValue;
-    const uint32_t grid = (uint32_t)std::min<unsigned long long>((p.n + 255) / 256, 4096);
-    hipLaunchKernelGGL(patch_scatter_kernel, dim3(grid), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
 namespace {
 
 // the device buffers of one diff: tile records, tile starts, the totals; the stream once its size is known
@@ -471,71 +450,6 @@ int fwgpu_debug_diff_rates(const fwgpu_image *base, const fwgpu_image *next, flo
         (void)hipGetLastError();
         return fail(FWGPU_ERR_DEVICE, std::string("debug_diff_rates: ") + hipGetErrorString(e));
     }
-    return FWGPU_OK;
-}
-
-int fwgpu_packed_apply_diff(fwgpu_regressor *r, const uint8_t *diff, uint64_t len, uint64_t *applied) {
-    if (!r || (len && !diff)) return fail(FWGPU_ERR_INVALID, "NULL argument");
-    if (applied) *applied = 0;
-    if (!r->packed()) return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the regressor's FFM weights are f32, not the file's f16 buckets: a byte diff of two inference files does not apply to it");
-    if (r->file_quantized_at_load)
-        return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the regressor's file was quantised at load: its buckets are not the file's bytes");
-    if (!r->file_header_bytes)
-        return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the regressor has no inference file behind it (made by fwgpu_pack_regressor: refresh it with that call; or loaded from a file that carries optimizer state)");
-    // the file: header | LR weights (f32) | {increment, min} | buckets
-    const uint64_t hb = r->file_header_bytes, lr_bytes = r->lr_len * 4, q_at = lr_bytes + 8, q_bytes = r->ffm_len * 2;
-    const uint64_t file_bytes = hb + q_at + q_bytes;
-    uint64_t entries = 0, in_header = 0;
-    int st = diffstream::walk(diff, len, file_bytes, [&](uint64_t index, uint8_t) { in_header += index < hb; }, &entries);
-    if (st) return fail(FWGPU_ERR_FORMAT, std::string("packed_apply_diff: ") + diffstream::status_text(st));
-    if (in_header) return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the model's header changed: load the file");
-    if (!entries) return FWGPU_OK;
-    uint8_t q_header[8];
-    memcpy(q_header, &r->q_increment, 4);
-    memcpy(q_header + 4, &r->q_min, 4);
-    std::vector<unsigned long long> index;
-    std::vector<uint8_t> to;
-    index.reserve(entries);
-    to.reserve(entries);
-    diffstream::walk(diff, len, file_bytes, [&](uint64_t at, uint8_t v) {
-        const uint64_t j = at - hb;
-        if (j >= lr_bytes && j < q_at) {
-            q_header[j - lr_bytes] = v;
-        } else {
-            index.push_back(j);
-            to.push_back(v);
-        }
-    });
-    FWGPU_HIP(hipSetDevice(r->device));
-    FWGPU_HIP(hipDeviceSynchronize());
-    if (!index.empty()) {
-        // one allocation: the indices, then the bytes
-        uint8_t *d_entries = nullptr;
-        const size_t n = index.size();
-        if (hipMalloc((void **)&d_entries, n * 9) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(FWGPU_ERR_OOM, "packed_apply_diff: no device memory for the entries");
-        }
-        PatchArgs p{};
-        p.index = reinterpret_cast<const unsigned long long *>(d_entries);
-        p.to = d_entries + n * 8;
-        p.n = n;
-        p.lr_bytes = lr_bytes;
-        p.q_at = q_at;
-        p.q_bytes = q_bytes;
-        p.lr = reinterpret_cast<uint8_t *>(r->d_lr);
-        p.q = reinterpret_cast<uint8_t *>(r->d_ffm_q);
-        hipError_t e = hipMemcpy(d_entries, index.data(), n * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_entries + n * 8, to.data(), n, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = launch_patch_scatter(p, 0);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        (void)hipFree(d_entries);
-        if (e != hipSuccess) return fail(FWGPU_ERR_DEVICE, std::string("packed_apply_diff: ") + hipGetErrorString(e));
-    }
-    memcpy(&r->q_increment, q_header, 4);
-    memcpy(&r->q_min, q_header + 4, 4);
-    r->weights_epoch++;  // (context caches set up before, fwgpu_packed_enable_caches, are stale from here on)
-    if (applied) *applied = entries;
     return FWGPU_OK;
 }
 

@@ -251,6 +251,14 @@ class Image:
         stream, changed = _two_call(lambda out, cap, n, ch: self.L.fwgpu_image_diff(self.h, nxt.h, out, cap, n, ch), first_cap=1 << 20)  # (one call when little changed)
         return (stream, changed) if with_changed else stream
 
+    def apply_diff(self, diff: bytes) -> int:
+        """patches the image in place from a byte-diff stream, decoded on the device: read() then gives apply_diff_bytes of the old bytes.
+        A bad stream raises with ERR_FORMAT and changes nothing.  Returns the number of entries -- fwgpu_image_apply_diff"""
+        d = np.frombuffer(diff, dtype=np.uint8)
+        n = C.c_uint64(0)
+        capi.check(self.L.fwgpu_image_apply_diff(self.h, capi.ptr(d), d.size, C.byref(n)))
+        return n.value
+
     def close(self):
         if self.h:
             self.L.fwgpu_image_free(self.h)
@@ -283,4 +291,30 @@ def debug_diff_rates(base: Image, nxt: Image):
     """milliseconds by device events: (size pass, tile scan, emit pass, device-to-device copy of one weights section) -- fwgpu_debug_diff_rates"""
     ms = np.zeros(4, dtype=np.float32)
     capi.check(capi.lib().fwgpu_debug_diff_rates(base.h, nxt.h, capi.ptr(ms)))
+    return tuple(float(x) for x in ms)
+
+
+def debug_diff_decode(diff: bytes, end: int, device: int = 0):
+    """the decoder's three kernels alone on a stream whose entries must lie below `end` (fwgpu_debug_diff_decode) -> (indices, bytes) as uint64
+    and uint8 arrays; a bad stream raises with ERR_FORMAT and the host reader's message"""
+    d = np.frombuffer(diff, dtype=np.uint8)
+    L = capi.lib()
+    index, to = np.zeros(d.size // 2, dtype=np.uint64), np.zeros(d.size // 2, dtype=np.uint8)  # (an entry is two bytes at least)
+    n, status = C.c_uint64(0), C.c_int32(0)
+    capi.check(L.fwgpu_debug_diff_decode(device, capi.ptr(d), d.size, end, capi.ptr(index), capi.ptr(to), index.size, C.byref(n), C.byref(status)))
+    return index[: n.value], to[: n.value]
+
+
+def debug_decode_geometry() -> int:
+    """the bytes of one tile of the decode kernels (fwgpu_debug_decode_geometry)"""
+    t = C.c_uint32(0)
+    capi.check(capi.lib().fwgpu_debug_decode_geometry(C.byref(t)))
+    return t.value
+
+
+def debug_decode_rates(diff: bytes, end: int, device: int = 0):
+    """milliseconds by device events: (summary pass, tile scan, apply pass, device-to-device copy of the stream) -- fwgpu_debug_decode_rates"""
+    d = np.frombuffer(diff, dtype=np.uint8)
+    ms = np.zeros(4, dtype=np.float32)
+    capi.check(capi.lib().fwgpu_debug_decode_rates(device, capi.ptr(d), d.size, end, capi.ptr(ms)))
     return tuple(float(x) for x in ms)

@@ -952,10 +952,26 @@ int fwgpu_image_diff(const fwgpu_image *base, const fwgpu_image *next, uint8_t *
  * r must come from fwgpu_model_load_packed on an inference file that was already quantised (dequantize_weights = true): its tables are
  * that file's bytes.  FWGPU_ERR_INVALID, with the reason: an f32 regressor, a product of fwgpu_pack_regressor (no file behind it: refresh it
  * with that call), a packed regressor whose file was quantised at load, and a stream with an entry in the file's header ("the model's header
- * changed: load the file").  A bad stream is FWGPU_ERR_FORMAT.  In all these cases r is as it was and usable.  Entries in the FFM block's 8-byte
- * header update the two launch constants; all others are scattered by one kernel, byte by byte.  The call waits for the device; the caller
- * must not have predict launches of r in flight on other streams (fwgpu_pack_regressor's refresh contract).  *applied (may be NULL): entries. */
+ * changed: load the file").  A bad stream is FWGPU_ERR_FORMAT.  In all these cases r is as it was and usable.  The raw stream is uploaded and
+ * decoded on the device (csrc/patch_apply.hip: summary pass, tile scan, apply pass); entries in the FFM block's 8-byte header update the two
+ * launch constants, all others are stored into the tables byte by byte.  The call waits for the device; the caller must not have predict
+ * launches of r in flight on other streams (fwgpu_pack_regressor's refresh contract).  *applied (may be NULL): entries. */
 int fwgpu_packed_apply_diff(fwgpu_regressor *r, const uint8_t *diff, uint64_t len, uint64_t *applied);
+/* Patches an image in place from such a stream: afterwards fwgpu_image_read gives the bytes fwgpu_diff_apply_bytes gives on the image's old
+ * bytes.  The weights section is patched by the same three kernels; entries in the header are patched on the host by a walk of the stream's
+ * prefix, which ends at the first entry behind the header.  A bad stream is FWGPU_ERR_FORMAT and the image is unchanged; an empty stream
+ * applies nothing.  *applied (may be NULL): entries. */
+int fwgpu_image_apply_diff(fwgpu_image *img, const uint8_t *diff, uint64_t len, uint64_t *applied);
+/* debug: the stream uploaded, the decode kernels run with target end `end` (one past the last index an entry may have), the first min(*entries,
+ * cap) entries returned in index[] and to[].  *status: the stream's status as csrc/diff_stream.h's walk gives it.  A bad stream is
+ * FWGPU_ERR_FORMAT with that status's text, as fwgpu_diff_apply_bytes words it; nothing is returned then and *entries is not defined. */
+int fwgpu_debug_diff_decode(int device, const uint8_t *diff, uint64_t len, uint64_t end, uint64_t *index, uint8_t *to, uint64_t cap,
+                            uint64_t *entries, int32_t *status);
+/* debug (scripts/bench_publish_diff.py): milliseconds, by device events, of the summary pass, the tile scan, the apply pass (into a pair of
+ * arrays, every entry stored) and a device-to-device copy of the stream's len bytes, after the stream is on the device */
+int fwgpu_debug_decode_rates(int device, const uint8_t *diff, uint64_t len, uint64_t end, float *ms4);
+/* debug: the bytes of one tile of the decode kernels */
+int fwgpu_debug_decode_geometry(uint32_t *tile_bytes);
 /* debug: two host arrays uploaded, the three kernels run, the stream returned (two-call protocol as fwgpu_diff_bytes) */
 int fwgpu_debug_diff(int device, const uint8_t *a, const uint8_t *b, uint64_t n, uint64_t base_offset, uint64_t prev_index, uint8_t *out,
                      uint64_t cap, uint64_t *written, uint64_t *changed);

@@ -9,6 +9,10 @@ published weights section stays on the device, the next one is diffed against it
   host      fwgpu_model_save_inference of the next file + both files read + fwgpu_diff_bytes (the base file is there from the last publish; its
             save is timed too and reported beside)
   apply     fwgpu_packed_apply_diff on the regressor loaded from the base file  vs  fwgpu_model_load_packed of the next file
+  image     fwgpu_image_apply_diff on the image loaded from the base file  vs  fwgpu_image_load of the next file
+  decode    the decoder's three kernels by device events beside a device-to-device copy of the stream's bytes (fwgpu_debug_decode_rates)
+  --parent_tree DIR   a built tree of the parent commit: its library and this one apply the stream in fresh processes, alternately, --repeats times
+            each (every process: load the base file packed, apply three times); the whole calls go to --ab_out under the stream's case name
 Both streams must be byte-identical or the script fails.  Medians of --repeats (>= 5) repetitions with min - max.  The three kernels' times by device
 events stand beside a device-to-device copy of one weights section in the same run (fwgpu_debug_diff_rates).  Files go to a memory-backed directory.
 THE BAR: the device route's slowest whole call is faster than the host route's fastest.  Needs a GPU: no fallback.
@@ -25,11 +29,24 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+CHILD = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "--apply_child" else None  # tree, base file, stream file
+sys.path.insert(0, CHILD[0] if CHILD else ROOT)
 import fwumious_wabbit_amd as fw  # noqa: E402
 from fwumious_wabbit_amd import capi  # noqa: E402
 from fwumious_wabbit_amd import persistence as P  # noqa: E402
 from fwumious_wabbit_amd.feed import VwNamespaceMap  # noqa: E402
+
+if CHILD:  # one process of the A/B: whichever tree's package was imported above
+    stream = open(CHILD[2], "rb").read()
+    _, _, served = P.new_regressor_from_filename(CHILD[1], immutable=True, packed=True)
+    out = []
+    for _ in range(3):
+        t = time.perf_counter()
+        served.apply_diff(stream)
+        out.append(time.perf_counter() - t)
+    served.close()
+    print("APPLY_S " + json.dumps(out), flush=True)
+    sys.exit(0)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "publish_diff.json"))
@@ -39,6 +56,8 @@ ap.add_argument("--examples", type=int, default=2000)
 ap.add_argument("--dir", default="/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None)
 ap.add_argument("--pin_extremes", action="store_true", help="write +x and -x, x beyond every trained weight, into the last two FFM weights before the "
                 "base publish: the quantiser's rounded extremes, and with them its 8-byte header, then stay put between the two publishes")
+ap.add_argument("--parent_tree", default=None)
+ap.add_argument("--ab_out", default=os.path.join(ROOT, "profiles", "publish_apply_parent_ab.json"))
 ap.add_argument("--commit", default=None, help="recorded as git_commit where the tree runs without its git metadata")
 a = ap.parse_args()
 assert a.repeats >= 5, "at least 5 repetitions"
@@ -92,7 +111,8 @@ if a.pin_extremes:
     re.table_write(capi.TABLE_FFM_W, [x, -x], offset=n_ffm - 2)
 say(f"regressor trained on {a.examples} examples" + (f", extremes pinned at +-{x}" if a.pin_extremes else ""))
 times = {k: [] for k in ("capture_base", "capture_next", "image_diff", "device_route", "save_base", "save_next", "host_diff", "host_route",
-                         "apply_diff", "load_packed")}
+                         "apply_diff", "load_packed", "image_apply_diff", "image_load")}
+decode_ms, ab = [], {"this": [], "parent": []}
 kernel_ms = []
 with tempfile.TemporaryDirectory(dir=a.dir) as tmp:
     f0, f1 = os.path.join(tmp, "publish0.fw"), os.path.join(tmp, "publish1.fw")
@@ -157,6 +177,30 @@ with tempfile.TemporaryDirectory(dir=a.dir) as tmp:
         fresh.close()
         say(f"repeat {rep}: apply_diff {times['apply_diff'][-1]:8.4f} s   load_packed {times['load_packed'][-1]:8.3f} s")
     served.close()
+    # ---- an image patched against an image reloaded
+    img = P.Image.load(f0)
+    for rep in range(a.repeats):
+        n, s = timed(lambda: img.apply_diff(stream))
+        times["image_apply_diff"].append(s)
+        assert n == changed
+        nxt, s = timed(lambda: P.Image.load(f1))
+        times["image_load"].append(s)
+        if rep == 0:
+            assert img.diff(nxt) == b"", "the patched image differs from the one loaded from the next file"
+        nxt.close()
+        decode_ms.append(list(P.debug_decode_rates(stream, header_bytes + weights_bytes)))
+        say(f"repeat {rep}: image apply_diff {times['image_apply_diff'][-1]:8.4f} s   image load {times['image_load'][-1]:8.3f} s   kernels {decode_ms[-1]}")
+    img.close()
+    if a.parent_tree:
+        sf = os.path.join(tmp, "stream.bin")
+        open(sf, "wb").write(stream)
+        for rep in range(a.repeats):
+            for who, tree in (("parent", a.parent_tree), ("this", ROOT)):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--apply_child", tree, f0, sf], capture_output=True, text=True, timeout=300)
+                line = [l for l in r.stdout.splitlines() if l.startswith("APPLY_S ")]
+                assert r.returncode == 0 and line, r.stderr[-2000:]
+                ab[who].append(json.loads(line[0][8:]))
+                say(f"A/B repeat {rep}: {who:6s} apply_diff {ab[who][-1]}")
 
 
 def stat(xs):
@@ -172,7 +216,7 @@ out = {"shape": dict(fields=F, ffm_k=K, bit_precision=a.bits, ffm_bit_precision=
        "identical": "the device's stream, the host's stream of the two files: every byte; patched and reloaded regressors: checksums of both tables"}
 out.update({k: stat(v) for k, v in times.items()})
 out["host_route_with_both_saves"] = stat(np.array(times["host_route"]) + np.array(times["save_base"]))
-out["pcie_bytes"] = dict(device_route=len(stream) + 8 + 12 + 16, host_route=weights_bytes, apply_diff=9 * changed, load_packed=weights_bytes)
+out["pcie_bytes"] = dict(device_route=len(stream) + 8 + 12 + 16, host_route=weights_bytes, apply_diff=len(stream) + 16, load_packed=weights_bytes)
 km = np.median(np.array(kernel_ms), axis=0)
 copy_rate = 2 * weights_bytes / (km[3] * 1e-3)
 out["kernels"] = dict(ms_all=kernel_ms, tile_bytes=P.debug_diff_geometry(),
@@ -184,6 +228,25 @@ for k in ("size_pass", "emit_pass"):
     out["kernels"][k]["share_of_device_copy_rate"] = out["kernels"][k]["bytes_per_s"] / copy_rate
 out["bar_met"] = bool(out["device_route"]["max_s"] < out["host_route"]["min_s"])
 out["apply_faster_than_reload"] = bool(out["apply_diff"]["max_s"] < out["load_packed"]["min_s"])
+out["image_apply_faster_than_reload"] = bool(out["image_apply_diff"]["max_s"] < out["image_load"]["min_s"])
+dm = np.median(np.array(decode_ms), axis=0)
+out["decode_kernels"] = dict(ms_all=decode_ms, tile_bytes=P.debug_decode_geometry(), stream_bytes=len(stream),
+                             summary_pass=dict(median_ms=float(dm[0]), bytes_per_s=len(stream) / (dm[0] * 1e-3)),
+                             tile_scan=dict(median_ms=float(dm[1])),
+                             apply_pass=dict(median_ms=float(dm[2]), bytes_per_s=(len(stream) + 9 * changed) / (dm[2] * 1e-3)),
+                             device_copy=dict(median_ms=float(dm[3]), bytes_per_s=2 * len(stream) / (dm[3] * 1e-3)))
+if a.parent_tree:
+    case = "pinned" if a.pin_extremes else "as_trained"
+    prev = json.load(open(a.ab_out)) if os.path.exists(a.ab_out) else {}
+    first = {k: [x[0] for x in v] for k, v in ab.items()}  # a process's first call: what a server that is patched once pays
+    later = {k: [y for x in v for y in x[1:]] for k, v in ab.items()}
+    prev[case] = dict(stream_bytes=len(stream), changed_bytes=changed, processes_each=a.repeats, order="parent, this, parent, this, ...",
+                      first_call={k: stat(v) for k, v in first.items()}, later_calls={k: stat(v) for k, v in later.items()},
+                      reload=out["load_packed"],
+                      this_slowest_below_parent_fastest=bool(max(first["this"] + later["this"]) < min(first["parent"] + later["parent"])),
+                      this_slowest_below_reload_fastest=bool(max(first["this"] + later["this"]) < out["load_packed"]["min_s"]))
+    json.dump(prev, open(a.ab_out, "w"), indent=1)
+    print(json.dumps(prev[case], indent=1))
 out["verdict"] = (("the device route's slowest call is faster than the host route's fastest" if out["bar_met"] else "THE BAR IS NOT MET") +
                   f": device {out['device_route']['median_s']:.3f} s, host {out['host_route']['median_s']:.3f} s; apply_diff "
                   f"{out['apply_diff']['median_s']:.4f} s against load_packed {out['load_packed']['median_s']:.3f} s")
