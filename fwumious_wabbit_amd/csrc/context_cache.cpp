@@ -297,7 +297,9 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
     for (uint32_t i = 0; i < b->n; i++)
         if (cache_of_example[i] >= n_caches) return fail(FWGPU_ERR_INVALID, "set_caches: cache_of_example holds an index >= n_caches");
     // one allocation: d_T of every cache, d_dcf of every cache, base [n_caches] (8-byte slots), then cache_of [n]
-    const size_t table = 2 * (size_t)n_caches * sizeof(float *), base = (((size_t)n_caches * sizeof(float)) + 7) & ~(size_t)7;
+    // (a deep head, fwgpu_enable_head_requests: base holds every cache's triangle row, F (F + 1) / 2 floats each)
+    const size_t F = b->owner->cfg.ffm_num_fields, per_cache = b->owner->nn.n_layers ? F * (F + 1) / 2 : 1;
+    const size_t table = 2 * (size_t)n_caches * sizeof(float *), base = (((size_t)n_caches * per_cache * sizeof(float)) + 7) & ~(size_t)7;
     std::vector<unsigned char> host(table + base + (size_t)b->n * sizeof(uint32_t), 0);
     const float **tp = reinterpret_cast<const float **>(host.data());
     for (uint32_t c = 0; c < n_caches; c++) {
@@ -359,6 +361,25 @@ int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *
     if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (enabled) *enabled = r->packed_caches ? 1 : 0;
     if (weights_epoch) *weights_epoch = r->weights_epoch;
+    return FWGPU_OK;
+}
+
+int fwgpu_enable_head_requests(fwgpu_regressor *r) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    const char *why = nullptr;
+    if (r->packed()) why = "a packed regressor has no deep head route";
+    else if (!r->nn.n_layers) why = "the regressor has no deep head: the requests route serves it without a switch";
+    else if (r->cfg.ffm_k == 0) why = "the model has no FFM block";
+    else if (r->cfg.ffm_k % 4 != 0) why = "ffm_k is no multiple of 4 (the requests kernel has no one-float-per-lane form)";
+    else if (r->cfg.ffm_num_fields > 256) why = "more than 256 fields";
+    if (why) return fail(FWGPU_ERR_INVALID, std::string("enable_head_requests: ") + why);
+    r->head_requests = true;
+    return FWGPU_OK;
+}
+
+int fwgpu_head_requests_state(const fwgpu_regressor *r, int *enabled) {
+    if (!r || !enabled) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *enabled = r->head_requests ? 1 : 0;
     return FWGPU_OK;
 }
 

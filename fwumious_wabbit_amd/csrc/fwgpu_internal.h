@@ -485,6 +485,19 @@ struct RequestsShape {
 bool requests_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out);
 // rows: rows of a field in flight per lane on a packed table -- 0 = the default, 4 or 8 (an f32 table always runs its own depth)
 hipError_t launch_requests(const RequestsParams &p, const RequestsShape &shape, hipStream_t stream, int rows = 0);
+// ... on a model with a deep head (requests_head.hip; fwgpu_enable_head_requests): the same batch and set, the head's input x in place of the logit
+struct RequestsHeadParams {
+    RequestsParams q;               // (q.base: [n_caches * NT] every cache's triangle row from S alone; q.pred, q.ffm_q are not read)
+    const uint16_t *lr_combo;       // combo slot of each LR entry
+    const float *label;             // [n] and importance [n]
+    const float *importance;
+    float *xbuf;                    // [n * X] the head's inputs
+    float *yi;                      // [2 n] {label, importance} where head_step reads them
+    uint32_t C, NT, X;              // combo slots, F (F + 1) / 2 triangle slots, C + NT
+};
+// false: one wave's slices and triangle row do not fit lds_limit bytes
+bool requests_head_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out);
+hipError_t launch_requests_head(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream);
 // fwgpu_setup_cache on a packed regressor (fwgpu_packed_enable_caches): the context's entries, ordered by field, -> the cache's T, dcf and cnt
 struct PackedCacheBuild {
     const uint16_t *ffm_q;
@@ -566,7 +579,7 @@ struct fwgpu_batch {
     std::unique_ptr<fwgpu::HostBatch> host_copy;  // entry batches with an example of more than 4096 FFM features / LR entries: walked example by example (regressor.cpp)
     // a cache per example (fwgpu_batch_set_caches): predict-only launches take the requests route (requests.hip)
     std::vector<const fwgpu_block_cache *> req_caches;  // the set (empty: none attached)
-    void *req_dev = nullptr;                            // one allocation: the pointer table [2 * set], base [set], cache_of [n]
+    void *req_dev = nullptr;                            // one allocation: the pointer table [2 * set], base [set] (head requests: [set * NT]), cache_of [n]
     size_t req_dev_bytes = 0;
     const float *const *req_T = nullptr;
     float *req_base = nullptr;
@@ -596,6 +609,7 @@ struct fwgpu_regressor {
     // fwgpu_pack_regressor's refresh in place)
     bool packed_caches = false;
     uint64_t weights_epoch = 0;
+    bool head_requests = false;  // fwgpu_enable_head_requests: the one-way switch that lets a deep-head model take the requests route (requests_head.hip)
     int placement_tries = 0;                     // candidate allocations timed for d_ffm_acc (regressor.cpp: place_ffm_acc)
     float placement_ms_lo = 0, placement_ms_hi = 0;  // fastest / slowest pair probe among them
     float placement_ms_single = 0;                    // the same probe on the weight table alone

@@ -313,7 +313,7 @@ static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int up
 const char *requests_refusal(const fwgpu_regressor *r, const fwgpu_batch *b) {
     const uint32_t k = r->cfg.ffm_k, F = r->cfg.ffm_num_fields;
     if (r->packed() && !r->packed_caches) return "a packed regressor keeps no device-side context cache";
-    if (r->nn.n_layers) return "models with a deep head are not served by the requests route (fwgpu_batch_set_cache serves them)";
+    if (r->nn.n_layers && !r->head_requests) return "models with a deep head are not served by the requests route (fwgpu_batch_set_cache serves them)";
     if (b->records) return "a record batch is not served by the requests route (an entry batch of the filtered buffers is)";
     if (b->host_copy) return "the batch holds an oversize example (more than 4096 entries of a kind, or beyond the fused kernel's LDS)";
     if (k == 0) return "the model has no FFM block";
@@ -325,14 +325,16 @@ const char *requests_refusal(const fwgpu_regressor *r, const fwgpu_batch *b) {
 
 // predict-only launch of an entry batch with a cache per example: base(S) of every cache of the set, then one wavefront per candidate, on `stream`
 // (`rows`: the packed predict kernel's rows in flight, 0 = its default -- fwgpu_debug_requests_time)
+static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const RequestsParams &q, hipStream_t stream);
 static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream, int rows = 0) {
     if (update) return fail(FWGPU_ERR_INVALID, "a batch with a cache per example (fwgpu_batch_set_caches) is predict-only: update must be 0");
     if (const char *why = requests_refusal(r, b)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + why);
     for (const fwgpu_block_cache *c : b->req_caches)
         if (cache_is_stale(r, c)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + kStaleCache);
     const uint32_t F = r->cfg.ffm_num_fields, k = r->cfg.ffm_k, R = F * k;
+    const bool head = r->nn.n_layers != 0;  // (fwgpu_enable_head_requests: requests_refusal let it through)
     RequestsShape shape;
-    if (!requests_launch_shape(F, R, b->max_ffm, r->lds_per_cu, &shape))
+    if (!head && !requests_launch_shape(F, R, b->max_ffm, r->lds_per_cu, &shape))
         return fail(FWGPU_ERR_RANGE, "requests route: min(fields, the batch's largest FFM entry count) * F * k floats of one candidate do not fit the 160 KiB LDS");
     RequestsParams p{};
     p.ffm_w = r->packed() ? nullptr : r->d_ffm_w;
@@ -358,6 +360,7 @@ static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hi
     p.R = R;
     p.slots = shape.slots;
     p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
+    if (head) return run_batch_head_requests(r, b, p, stream);
     LaunchRecord l{};
     l.family = r->packed() ? FWGPU_KERNEL_PACKED_REQUESTS : FWGPU_KERNEL_REQUESTS;
     l.chunks = (int32_t)shape.chunks;
@@ -381,7 +384,8 @@ static bool head_predict_batched(const fwgpu_regressor *r, const fwgpu_batch *b,
     const uint32_t k = r->cfg.ffm_k, R = k * r->cfg.ffm_num_fields;
     return k && k % 4 == 0 && b->aligned4 && (R <= 256 || (R <= 512 && 256 % k == 0)) && r->launch.kernel_version != 1;
 }
-static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_t stream) {
+// pred_x / pred_yi for a batch of n examples (grown, never shrunk: the stream is waited for before the old buffers go)
+static int ensure_pred_buffers(fwgpu_regressor *r, const fwgpu_batch *b, hipStream_t stream) {
     const uint32_t X = r->nn.X;
     if (r->pred_cap < b->n) {
         FWGPU_HIP(hipStreamSynchronize(stream));
@@ -395,22 +399,60 @@ static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_
         }
         r->pred_cap = b->n;
     }
-    LaunchPlan plan;
-    const char *why = nullptr;
-    int rc = plan_head_inputs(r, b, plan, &why);
-    if (rc) return fail(rc, why);
-    if ((rc = fresh_work_counter(b, plan.p, stream))) return rc;
-    record_launch(r, plan, false, r->cfg.optimizer);
-    FWGPU_HIP(launch_example_kernel(plan.p, r->cfg.optimizer, false, plan.grid, plan.threads, stream));
+    return FWGPU_OK;
+}
+// the layers over pred_x, slab by slab, into the batch's predictions
+static int head_predict_slabs(fwgpu_regressor *r, fwgpu_batch *b, hipStream_t stream) {
     fwgpu_split view;
     view.owner = r;
     view.d_x = r->pred_x;
     view.d_g = r->pred_yi;
     for (uint32_t first = 0; first < b->n; first += kHeadPredictSlab) {
-        rc = head_step(r, &view, first, std::min(kHeadPredictSlab, b->n - first), b->pred + first, /*update=*/false, stream);
+        const int rc = head_step(r, &view, first, std::min(kHeadPredictSlab, b->n - first), b->pred + first, /*update=*/false, stream);
         if (rc) return rc;
     }
     return FWGPU_OK;
+}
+static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_t stream) {
+    int rc = ensure_pred_buffers(r, b, stream);
+    if (rc) return rc;
+    LaunchPlan plan;
+    const char *why = nullptr;
+    rc = plan_head_inputs(r, b, plan, &why);
+    if (rc) return fail(rc, why);
+    if ((rc = fresh_work_counter(b, plan.p, stream))) return rc;
+    record_launch(r, plan, false, r->cfg.optimizer);
+    FWGPU_HIP(launch_example_kernel(plan.p, r->cfg.optimizer, false, plan.grid, plan.threads, stream));
+    return head_predict_slabs(r, b, stream);
+}
+
+// ... with a cache per example (fwgpu_enable_head_requests): every cache's triangle row, one wavefront per candidate forms its x from the cache and its
+// own few features (requests_head.hip), then the same layers.  Any batch size: the frozen weights order nothing, and there is no other route to fall to.
+static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const RequestsParams &q, hipStream_t stream) {
+    RequestsShape shape;
+    if (!requests_head_launch_shape(q.F, q.R, b->max_ffm, r->lds_per_cu, &shape))
+        return fail(FWGPU_ERR_RANGE, "requests route: min(fields, the batch's largest FFM entry count) * F * k + F (F + 1) / 2 floats of one candidate do not fit the 160 KiB LDS");
+    int rc = ensure_pred_buffers(r, b, stream);
+    if (rc) return rc;
+    RequestsHeadParams p{};
+    p.q = q;
+    p.q.slots = shape.slots;
+    p.lr_combo = b->lr_combo;
+    p.label = b->label;
+    p.importance = b->importance;
+    p.xbuf = r->pred_x;
+    p.yi = r->pred_yi;
+    p.C = r->cfg.num_combos;
+    p.NT = q.F * (q.F + 1) / 2;
+    p.X = r->nn.X;
+    LaunchRecord l{};
+    l.family = FWGPU_KERNEL_HEAD_REQUESTS;
+    l.chunks = (int32_t)shape.chunks;
+    l.threads = (int32_t)shape.threads;
+    l.lds_bytes = (int32_t)shape.lds_bytes;
+    launched(r, l);
+    FWGPU_HIP(launch_requests_head(p, shape, stream));
+    return head_predict_slabs(r, b, stream);
 }
 
 // the fused example kernel, the deep head (if any) per example inside it
@@ -443,7 +485,11 @@ int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStrea
     if (route) *route = taken;
     switch (taken) {
     case FWGPU_ROUTE_NONE: return FWGPU_OK;
-    case FWGPU_ROUTE_REQUESTS: return run_batch_requests(r, b, update, stream);
+    case FWGPU_ROUTE_REQUESTS: {
+        const int rc = run_batch_requests(r, b, update, stream);
+        if (route && rc == FWGPU_OK && r->nn.n_layers) r->pred_n = b->n;  // (head requests: x of every candidate is in pred_x)
+        return rc;
+    }
     case FWGPU_ROUTE_PACKED: return run_batch_packed(r, b, mode, update, stream);
     case FWGPU_ROUTE_HOST_WALK: return run_batch_by_example(r, b, update, stream);
     case FWGPU_ROUTE_HEAD_BATCHED: {
@@ -798,7 +844,7 @@ int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n) 
 
 int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats) {
     if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
-    if (r->last_route != FWGPU_ROUTE_HEAD_BATCHED || !r->pred_n || !r->pred_x)
+    if ((r->last_route != FWGPU_ROUTE_HEAD_BATCHED && r->last_route != FWGPU_ROUTE_REQUESTS) || !r->pred_n || !r->pred_x)
         return fail(FWGPU_ERR_INVALID, "head_inputs: the regressor's last batch launch was not a batched head predict");
     if (n_floats > (uint64_t)r->pred_n * r->nn.X) return fail(FWGPU_ERR_RANGE, "head_inputs: more floats than the last launch wrote (n * X)");
     FWGPU_HIP(hipDeviceSynchronize());  // (the launch may have run on a stream of the caller's)

@@ -13,7 +13,8 @@
 // for those.  Models with a deep head are served through the cache like any other (block_neural.rs:355, block_misc.rs:847, block_relu.rs:123: every block
 // behind the FFM block inherits forward_with_cache): the cache also keeps how many features it holds per field, which is what the head's input diagonal
 // needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (launch.cpp run_batch_head_predict), a smaller one
-// the per-example kernel.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
+// the per-example kernel; with --head_requests on the command (fwgpu_enable_head_requests) fwgpu_predictor_predict_requests serves such a model too,
+// through the head-input kernels of requests_head.hip.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
 // unless the command also holds --packed_context_cache: the model's regressor then gets fwgpu_packed_enable_caches, fw_setup_cache builds the
 // device cache from the packed table (no record cover: every cached call takes the ENTRY route), and fw_predict_with_cache,
 // fwgpu_predictor_predict_batch(with_cache) and fwgpu_predictor_predict_requests score the filtered candidate against it on the requests kernels.
@@ -236,11 +237,12 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         if (words[i] == "-i" || words[i] == "--initial_regressor") weights = words[i + 1];
         if (words[i] == "--device") device = std::atoi(words[i + 1].c_str());  // ours: which GPU serves
     }
-    bool packed = false, packed_caches = false;
+    bool packed = false, packed_caches = false, head_requests = false;
     for (const auto &w : words) {
         if (w.rfind("--initial_regressor=", 0) == 0) weights = w.substr(std::strlen("--initial_regressor="));
         if (w == "--packed_weights") packed = true;  // ours: the FFM weights stay f16 buckets on the device (fwgpu_model_load_packed)
         if (w == "--packed_context_cache") packed_caches = true;  // ours: ... and context caches are built from them (fwgpu_packed_enable_caches)
+        if (w == "--head_requests") head_requests = true;  // ours: a deep-head model takes the requests route (fwgpu_enable_head_requests)
     }
     if (packed_caches && !packed) {
         set_error("--packed_context_cache is valid only together with --packed_weights (an f32 predictor keeps its context cache without it)");
@@ -250,11 +252,25 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         set_error("Cannot resolve input weights file name");  // the reference panics here (lib.rs:164-167)
         return nullptr;
     }
+    if (head_requests) {  // the file's header decides, before a device is touched
+        fwgpu_model_instance *mi = nullptr;
+        fwgpu_nn_config nn{};
+        if (fwgpu_model_read_header(weights.c_str(), nullptr, &mi) != FWGPU_OK) return nullptr;
+        const int rc = fwgpu_mi_configs(mi, device, nullptr, nullptr, &nn);
+        fwgpu_mi_free(mi);
+        if (rc != FWGPU_OK) return nullptr;
+        if (nn.n_layers == 0 || packed) {
+            set_error(packed ? "--head_requests is not valid together with --packed_weights (a packed regressor has no deep head route)"
+                             : "--head_requests is valid only on a model with a deep head (fwgpu_predictor_predict_requests serves a headless model without it)");
+            return nullptr;
+        }
+    }
     auto model = std::make_shared<SharedModel>();
     if ((packed ? fwgpu_model_load_packed(weights.c_str(), device, &model->vw, &model->mi, &model->re)
                 : fwgpu_model_load(weights.c_str(), device, /*immutable=*/1, &model->vw, &model->mi, &model->re)) != FWGPU_OK)
         return nullptr;
     if (packed_caches && fwgpu_packed_enable_caches(model->re) != FWGPU_OK) return nullptr;
+    if (head_requests && fwgpu_enable_head_requests(model->re) != FWGPU_OK) return nullptr;  // (a model without a head: an error, with the reason)
     if (fwgpu_mi_configs(model->mi, device, nullptr, &model->tr, nullptr) != FWGPU_OK) return nullptr;
     auto p = std::make_unique<FfiPredictor>();
     p->model = model;
@@ -692,7 +708,7 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
     if (m.re->packed() && !m.re->packed_caches)
         return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a --packed_weights predictor keeps no device cache") + kSee);
     if (m.re->cfg.ffm_k == 0) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a model without an FFM block keeps no device cache") + kSee);
-    if (m.re->nn.n_layers) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
+    if (m.re->nn.n_layers && !m.re->head_requests) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
     std::vector<const fwgpu_block_cache *> caches;  // the set: every predictor's cache once
     std::vector<uint32_t> cache_of_request(n_requests);
     for (uint32_t r = 0; r < n_requests; r++) {
@@ -806,8 +822,15 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
         if (rc == FWGPU_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess)
             rc = fail(FWGPU_ERR_DEVICE, "predict_requests: copy to the device failed");
     };
-    for (unsigned t = 0; t < T; t++) {  // (labels, importances and combo slots are not read by a predict-only launch of a model without a deep head)
+    const bool head = m.re->nn.n_layers != 0;
+    for (unsigned t = 0, ex0 = 0; t < T; t++) {  // (labels, importances and combo slots are not read by a predict-only launch of a model without a deep head)
         const HostBatch &src = host->parts[t]->hb;
+        if (head) {  // --head_requests: the head's input keeps one LR sum per combo slot, and head_step reads {label, importance}
+            up(eb->lr_combo + lb[t], src.lr_combo.data(), src.lr_combo.size() * sizeof(uint16_t));
+            up(eb->label + ex0, src.label.data(), src.label.size() * 4);
+            up(eb->importance + ex0, src.importance.data(), src.importance.size() * 4);
+            ex0 += (unsigned)src.label.size();
+        }
         up(eb->ffm_hash + fb[t], src.ffm_hash.data(), src.ffm_hash.size() * 4);
         up(eb->ffm_val + fb[t], src.ffm_val.data(), src.ffm_val.size() * 4);
         up(eb->ffm_fld + fb[t], src.ffm_fld.data(), src.ffm_fld.size());

@@ -572,6 +572,18 @@ class Regressor:
         check(self.L.fwgpu_packed_caches_state(self.h, C.byref(on), C.byref(ep)))
         return bool(on.value), ep.value
 
+    def enable_head_requests(self):
+        """one-way switch on an f32 regressor with a deep head: Batch.set_caches is accepted, and a predict-only launch of such a batch forms every
+        candidate's head input from its cache and its own features (csrc/requests_head.hip) before the layers run over the whole batch
+        -- fwgpu_enable_head_requests"""
+        check(self.L.fwgpu_enable_head_requests(self.h))
+
+    def head_requests_state(self) -> bool:
+        """whether enable_head_requests was called -- fwgpu_head_requests_state"""
+        on = C.c_int32(0)
+        check(self.L.fwgpu_head_requests_state(self.h, C.byref(on)))
+        return bool(on.value)
+
     def debug_requests_time(self, batch, rows=0, reps=20) -> float:
         """milliseconds per launch of the requests route of a batch with a set attached, by device events; rows: the packed predict kernel's rows
         in flight (4 or 8; 0 = the default) -- fwgpu_debug_requests_time"""

@@ -12,7 +12,11 @@
  *                                                         an error) lets such a predictor keep device context caches
  *                                                         (fwgpu_packed_enable_caches): fw_setup_cache builds one from the
  *                                                         packed table, the cached calls below and
- *                                                         fwgpu_predictor_predict_requests score filtered candidates.  NULL +
+ *                                                         fwgpu_predictor_predict_requests score filtered candidates;
+ *                                                         `--head_requests` (ours, only on a model with a deep head and
+ *                                                         without --packed_weights, else an error) lets
+ *                                                         fwgpu_predictor_predict_requests serve such a model
+ *                                                         (fwgpu_enable_head_requests).  NULL +
  *                                                         fwgpu_last_error() on failure (the reference panics).
  *   lib.rs:187-205  clone_lite(prototype)                 cheap per-thread copy sharing the weights
  *   lib.rs:207-212  fw_predict(ptr, vw_text)              -> prediction, or -1.0 for EOF / a line that does not parse
@@ -58,7 +62,7 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint
  * host's worker threads; one entry batch with a cache per example follows (fwgpu_batch_set_caches), whose kernel's work per candidate
  * follows the candidate's own features.  FWGPU_ERR_INVALID, pointing to fwgpu_predictor_predict_batch: predictors of different
  * models, a predictor without a device cache (no fw_setup_cache yet, --packed_weights without --packed_context_cache, a model without an FFM block), a model with
- * a deep head.  Concurrent callers are not coalesced: each call is one launch under the model's mutex. */
+ * a deep head whose predictor was created without --head_requests.  Concurrent callers are not coalesced: each call is one launch under the model's mutex. */
 int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs,
                                      const uint32_t *n_inputs, float *const *out);
 

@@ -231,7 +231,7 @@ int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *cache);
  * next launch.  Like every change of a batch's contents, the call must not overlap a launch of the batch that is still in flight.
  * n_caches == 0 detaches; fwgpu_batch_set_cache on the same batch replaces the set, and the other way round.
  * FWGPU_ERR_INVALID, the batch left as it was: a record batch, an index >= n_caches, a cache of another regressor, a regressor with
- * a deep head or packed weights (without fwgpu_packed_enable_caches), a stale cache of a packed regressor, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
+ * a deep head (without fwgpu_enable_head_requests) or packed weights (without fwgpu_packed_enable_caches), a stale cache of a packed regressor, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
  * whose min(fields, largest FFM entry count of an example) * F * k floats exceed the 160 KiB LDS returns FWGPU_ERR_RANGE. */
 int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches,
                            const uint32_t *cache_of_example /* [examples of b] */);
@@ -602,11 +602,12 @@ int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 #define FWGPU_KERNEL_PACKED 3   /* ... its predict-only instantiation on a packed table */
 #define FWGPU_KERNEL_REQUESTS 4 /* the requests kernels (FWGPU_ROUTE_REQUESTS): [1] = ceil(R / 256), [6] = threads per workgroup, [7] = LDS bytes, [2]..[5] = 0 */
 #define FWGPU_KERNEL_PACKED_REQUESTS 5 /* ... their instantiation on a packed table (fwgpu_packed_enable_caches); the fields as FWGPU_KERNEL_REQUESTS */
+#define FWGPU_KERNEL_HEAD_REQUESTS 6 /* the head-input kernels of the requests route on a model with a deep head (fwgpu_enable_head_requests); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_LAUNCH_INFO_LEN 8
 int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
- * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED,
- * FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */
+ * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED
+ * or, on a model with a deep head, FWGPU_ROUTE_REQUESTS (fwgpu_enable_head_requests); FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */
 int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats);
 /* an f32 as serde_json / ryu prints it in the embedded JSON documents ("0.1", "1.0", "1e-7"); NUL-terminated */
 int fwgpu_debug_format_f32(float v, char *buf, uint32_t cap);
@@ -869,6 +870,16 @@ int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes);
  * sums of weights that no longer exist.  fwgpu_setup_cache on the same handle refills the cache at the current epoch. */
 int fwgpu_packed_enable_caches(fwgpu_regressor *r);
 int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *weights_epoch); /* either output may be NULL */
+/* ---- the requests route on a model with a deep head (opt-in).  fwgpu_enable_head_requests is a ONE-WAY switch on an f32 regressor with a deep
+ * head; FWGPU_ERR_INVALID with the reason for a regressor without a head, a packed regressor, ffm_k == 0, ffm_k % 4 != 0, more than 256 fields.
+ * Without it fwgpu_batch_set_caches refuses such a regressor as ever.  With it the call accepts the regressor, and a predict-only launch of the batch
+ * takes FWGPU_ROUTE_REQUESTS with the kernel family FWGPU_KERNEL_HEAD_REQUESTS (csrc/requests_head.hip): every cache's triangle row, one wavefront
+ * per candidate that forms the head's input x from its cache and its own few features, then the layers over the whole batch on the MFMA GEMMs, at any
+ * batch size.  x is bit-identical between launches, modes and candidate orders; fwgpu_debug_head_inputs serves it.  Still FWGPU_ERR_INVALID: record
+ * batches, oversize examples, rows off the 16-byte boundary, update != 0, a foreign cache, an index >= n_caches.  FWGPU_ERR_RANGE: a candidate whose
+ * (min(fields, largest FFM entry count) * F * k + F (F + 1) / 2) floats exceed the 160 KiB LDS. */
+int fwgpu_enable_head_requests(fwgpu_regressor *r);
+int fwgpu_head_requests_state(const fwgpu_regressor *r, int *enabled);
 /* debug: a cache's contents as the device holds them -- T [F * F * k], dcf [F], cnt [F], the epoch it was set up at (each may be NULL).  Waits for the device. */
 int fwgpu_debug_block_cache_read(const fwgpu_block_cache *cache, float *T, float *dcf, uint32_t *cnt, uint64_t *epoch);
 /* debug (scripts/bench_serving_packed_requests.py): milliseconds per launch, by device events over `reps` launches on the null stream, of the
