@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 from fwumious_wabbit_amd import capi
-from fwumious_wabbit_amd.feed import f32_from_text
+from fwumious_wabbit_amd.feed import VowpalParser, VwNamespaceMap, f32_from_text
+import text_token_cases as K
+from text_token_cases import _random_decimal
 
 _libc = ctypes.CDLL("libc.so.6")
 _libc.strtof.restype = ctypes.c_float
@@ -26,19 +28,6 @@ def _check(s):
         r = np.float32(_libc.strtof(s.encode(), None))
         assert (np.isnan(v) and np.isnan(r)) or _bits(v) == _bits(r), (s, v, r)
     return proven
-
-
-def _random_decimal(rng, max_digits=19, max_exp=40):
-    nd = rng.randint(1, max_digits)
-    ds = "".join(rng.choice("0123456789") for _ in range(nd))
-    if rng.random() < 0.6:
-        k = rng.randint(0, nd)
-        ds = ds[:k] + "." + ds[k:]
-    if rng.random() < 0.5:
-        ds += rng.choice("eE") + rng.choice(["", "+", "-"]) + "%02d" % rng.randint(0, max_exp)
-    if rng.random() < 0.3:
-        ds = rng.choice("+-") + ds
-    return ds
 
 
 def test_zero_point_digits():
@@ -114,3 +103,113 @@ def test_fallback_cap_on_short_decimals():
     for _ in range(n):
         unproven += not _check(_random_decimal(rng, max_digits=9, max_exp=20))
     assert unproven * 10000 <= n, unproven
+
+
+# ---------------------------------------------------------------- the token cases of the device tests (text_token_cases.py), on the host alone:
+# what tests/test_gpu_textparse_tokens.py stands on, so that its comparisons with the host parser cannot be vacuous
+def _host_parses(host, lines, n_ns=6):
+    """every line is an example for the host parser: one buffer, as many records as lines"""
+    text = b"\n".join(lines) + b"\n"
+    words, off, used, rc = host.parse_buffer(text, words_cap=len(text) + (n_ns + 16) * len(lines))
+    assert rc == capi.OK and used == len(text) and len(off) == len(lines) + 1, (rc, used, len(off), lines[len(off) - 1][:80])
+
+
+@pytest.fixture(scope="module")
+def host():
+    p = VowpalParser(VwNamespaceMap(K.CSV))
+    yield p
+    p.close()
+
+
+def test_number_families_agree_with_strtof_where_proven():
+    fams = K.number_families(K.SEED)
+    assert 18000 <= sum(len(v) for v in fams.values()) <= 22000
+    assert not any(K.usable(s) for s in fams.pop("host"))  # outside the grammar or never proven
+    for name, strings in fams.items():
+        proven = sum(_check(s) for s in strings)
+        assert proven >= 1, name
+        if name in K.DOUBTFUL:
+            assert proven < len(strings), name
+    assert all(_check(s) for s in fams["exact midpoints"])  # the fast path accepts an exact midpoint
+    assert set(K.DOUBTFUL) <= set(fams)
+
+
+def test_number_lines_are_mostly_the_devices(host):
+    lines, pos, takes, stops = K.number_lines(K.numbers(K.SEED))
+    pos, takes = np.array(pos), np.array(takes)
+    for p in range(4):  # an unproven number costs a host line: in every place most lines are predicted to stay on the device
+        assert (pos == p).sum() > 15000 and 2 * takes[pos == p].sum() > (pos == p).sum(), K.POSITIONS[p]
+    assert 1000 < (~takes).sum()  # ... and the other side is there to be counted
+    _host_parses(host, lines)
+    assert len(stops) > 60 and {p for _, p in stops} == {0, 1, 2, 3}
+    for line, _ in stops:
+        assert host.parse_buffer(line + b"\n")[3] == capi.ERR_PARSE, line
+    # label-free, for candidate mode: no importance
+    lines, pos, takes, stops = K.number_lines(K.numbers(K.SEED)[::97], label=False)
+    assert set(pos) == {1, 2, 3} and all(l[:1] == b"|" for l in lines) and all(l[:1] == b"|" for l, _ in stops)
+
+
+def test_group_cap_and_name_lines_are_what_they_claim(host):
+    groups = K.group_lines()
+    assert len({line for line, _ in groups}) == len(groups) > 50
+    for line, ntok in groups:
+        assert K.count_tokens(line) == ntok and len(line) + 1 <= 4096, line[:60]
+    _host_parses(host, [line for line, _ in groups])
+    # a namespace token at each of the indexes, in each kind
+    for i in K.GROUP_EDGES:
+        for ns, _ in K.GROUP_KINDS:
+            assert any(l[l.find(b"|"):].split()[i: i + 1] == [ns.encode()] for l, _ in groups), (i, ns)
+    assert sum(1 for line, _ in groups if line[:1] == b"|") >= 15
+    for cap, hi, lo in ((512, 4096, 0), (4096, 65536, 4096), (514, 65536, 4096)):
+        caps = K.cap_lines(cap, hi, lo)
+        assert [n for _, n in caps] == [cap - 1, cap, cap + 1]
+        for line, ntok in caps:
+            assert K.count_tokens(line) == ntok and lo < len(line) + 1 <= hi
+        _host_parses(host, [line for line, _ in caps])
+    for size in (4095, 4096, 4097, 65535, 65536, 65537):
+        line = K.sized_line(size)
+        assert len(line) + 1 == size and K.count_tokens(line) <= 4096
+        for o in range(16):
+            prefix = K.aligned(line, o)
+            assert len(prefix) % 16 == o and prefix.endswith(b"\n")
+            _host_parses(host, prefix[:-1].split(b"\n"))
+        _host_parses(host, [line])
+    nms = K.names(K.SEED)
+    assert {len(n) for n in nms} >= set(range(71)) and b"" in nms and b"NONE" in nms
+    assert any(min(n) >= 0x80 for n in nms if n) and any(b"|" in n[1:-1] for n in nms) and any(n.endswith(b"|") for n in nms)
+    assert not any(b":" in n or b" " in n or b"\n" in n or n[:1] == b"|" for n in nms)
+    lines, takes = K.name_lines(nms)
+    _host_parses(host, lines)
+    assert 0 < takes.count(False) < 20
+
+
+def _probes(where, mask):
+    """per name: how many occupied slots its lookup passes before its own, and whether it passes the table's last slot"""
+    return {nm: ((slot - home) & mask, slot < home) for nm, (home, slot) in where.items()}
+
+
+def test_big_map_has_a_probe_chain_and_a_wrap():
+    csv, nms, f32 = K.big_map(256)
+    assert len(set(nms)) == 256 and len(f32) == 3
+    mask, where = K.ns_table(nms)
+    assert mask == K.BIG_MASK  # 4 * 256 entries: csrc/parser_types.h build_ns_table
+    pr = _probes(where, mask)
+    assert max(d for d, _ in pr.values()) >= 2  # a chain of three: some lookup passes two occupied slots
+    assert any(w for _, w in pr.values())  # and some lookup goes on from slot `mask` to slot 0
+    assert {len(n.encode()) for n in nms} >= {1, 2, 3, 4} and any(len(n) < len(n.encode()) for n in nms)
+    assert all(p in nms for p in ("A", "AA", "AAA"))
+    und = K.undeclared_on_chain(nms)
+    assert und not in nms and K.fnv1a(und.encode()) & mask == mask and (mask in {s for _, s in where.values()})
+    for n in (255, 256, 257):
+        csv, nms, f32 = K.big_map(n)
+        vw = VwNamespaceMap(csv)
+        assert vw.num_namespaces == n and [vw.lookup(x)[1] for x in nms] == [x in f32 for x in nms]
+        assert K.ns_table(nms)[0] == (1023 if n <= 256 else 2047)
+        p = VowpalParser(vw)
+        lines = K.map_lines(nms, f32, n)
+        assert 200 < len(lines) < 400
+        named = {t[1:].split(b":")[0] for l in lines for t in l.split() if t[:1] == b"|"}
+        assert named == {x.encode() for x in nms}
+        _host_parses(p, lines, n_ns=n)
+        assert p.parse_buffer(("1 |%s a\n" % und).encode())[3] == capi.ERR_PARSE
+        p.close()
