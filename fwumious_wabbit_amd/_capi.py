@@ -27,6 +27,7 @@ TABLE_LR, TABLE_FFM_W, TABLE_FFM_ACC, TABLE_NN_W, TABLE_NN_ACC = 0, 1, 2, 3, 4
 ROUTE_NONE, ROUTE_FUSED, ROUTE_HEAD_BATCHED, ROUTE_HEAD_BATCHED_REFUSED, ROUTE_PACKED, ROUTE_HOST_WALK, ROUTE_REQUESTS = 0, 1, 2, 3, 4, 5, 6
 # fwgpu_debug_last_launch
 KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED, KERNEL_REQUESTS, KERNEL_PACKED_REQUESTS, KERNEL_HEAD_REQUESTS = 0, 1, 2, 3, 4, 5, 6
+KERNEL_HEAD_FUSED = 7
 LAUNCH_INFO = ("family", "chunks", "window", "chain", "no_kept_rows", "lds_keep", "threads", "lds_bytes")
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
@@ -259,6 +260,9 @@ def lib():
         "fwgpu_packed_caches_state": [vp, P(i32), P(u64)],
         "fwgpu_enable_head_requests": [vp],
         "fwgpu_head_requests_state": [vp, P(i32)],
+        "fwgpu_enable_fused_head": [vp],
+        "fwgpu_fused_head_state": [vp, P(i32), P(u64), P(u64)],
+        "fwgpu_debug_head_forward_time": [vp, u32, i32, u32, P(C.c_float), vp],
         "fwgpu_debug_block_cache_read": [vp, vp, vp, vp, P(u64)],
         "fwgpu_debug_requests_time": [vp, vp, i32, u32, P(f32)],
         "fwgpu_quantize_ffm_table": [vp, vp, u64, P(u64)],

@@ -610,6 +610,7 @@ struct fwgpu_regressor {
     bool packed_caches = false;
     uint64_t weights_epoch = 0;
     bool head_requests = false;  // fwgpu_enable_head_requests: the one-way switch that lets a deep-head model take the requests route (requests_head.hip)
+    bool fused_head = false;     // fwgpu_enable_fused_head: the one-way switch that sends small predict-only slabs through head_forward_fused_kernel (head_fused.hip)
     int placement_tries = 0;                     // candidate allocations timed for d_ffm_acc (regressor.cpp: place_ffm_acc)
     float placement_ms_lo = 0, placement_ms_hi = 0;  // fastest / slowest pair probe among them
     float placement_ms_single = 0;                    // the same probe on the weight table alone
@@ -867,4 +868,9 @@ int split_update(fwgpu_regressor *r, fwgpu_batch *b, fwgpu_split *sp, int mode, 
 // mini-batched deep head on the records' x (head.hip): forward, sigmoid, backward, one AdaGrad step per dense weight
 int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, float *d_pred, bool update, hipStream_t stream);
 void head_scratch_free(fwgpu_regressor *r);
+// the predict-only forward of the whole head in one launch, a workgroup per 32 examples (head_fused.hip).  head_fused_lds_bytes: the workgroup's LDS, 0 where the
+// kernel does not serve the regressor's head (it does not fit the CU's LDS: the caller keeps head_step)
+size_t head_fused_lds_bytes(const fwgpu_regressor *r);
+int head_forward_fused(fwgpu_regressor *r, const float *x, uint32_t n, float *d_pred, hipStream_t stream);
+constexpr uint32_t kHeadFusedThreads = 512;
 }  // namespace fwgpu

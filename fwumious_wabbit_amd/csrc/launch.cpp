@@ -380,7 +380,8 @@ static constexpr uint32_t kHeadPredictSlab = 32768;
 static bool head_predict_batched(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update) {
     static const bool env_off = getenv("FWGPU_HEAD_PREDICT_PER_EXAMPLE") != nullptr;  // A/B runs: the per-example forward for every launch
     const bool off = r->launch.head_predict >= 0 ? r->launch.head_predict == 0 : env_off;  // (fwgpu_debug_set_option 14 overrides the environment)
-    if (off || update || !r->nn.n_layers || mode != FWGPU_MODE_HOGWILD || b->n < 256 || b->emit_T) return false;
+    // (below 256 examples the per-example forward inside the fused example kernel, unless fwgpu_enable_fused_head gave small batches a head of their own)
+    if (off || update || !r->nn.n_layers || mode != FWGPU_MODE_HOGWILD || (b->n < 256 && !r->fused_head) || b->emit_T) return false;
     const uint32_t k = r->cfg.ffm_k, R = k * r->cfg.ffm_num_fields;
     return k && k % 4 == 0 && b->aligned4 && (R <= 256 || (R <= 512 && 256 % k == 0)) && r->launch.kernel_version != 1;
 }
@@ -401,14 +402,30 @@ static int ensure_pred_buffers(fwgpu_regressor *r, const fwgpu_batch *b, hipStre
     }
     return FWGPU_OK;
 }
+// fwgpu_enable_fused_head: a slab of at most this many examples goes through head_forward_fused_kernel (head_fused.hip) -- the largest measured size at which
+// the fused kernel's slowest run is below the GEMM route's fastest (profiles/head_fused.json, scripts/bench_head_fused.py: 0.166 ms against 0.218 ms at
+// 32 768, 0.036 against 0.045 at 4096; up to 1024 examples a single tile's 0.035 ms is SLOWER than the three GEMM launches' 0.015 - 0.019 ms)
+static constexpr uint32_t kHeadFusedMaxN = 32768;
 // the layers over pred_x, slab by slab, into the batch's predictions
 static int head_predict_slabs(fwgpu_regressor *r, fwgpu_batch *b, hipStream_t stream) {
     fwgpu_split view;
     view.owner = r;
     view.d_x = r->pred_x;
     view.d_g = r->pred_yi;
+    const size_t fused_lds = r->fused_head ? head_fused_lds_bytes(r) : 0;  // (0: a head beyond the CU's LDS keeps the GEMM route)
     for (uint32_t first = 0; first < b->n; first += kHeadPredictSlab) {
-        const int rc = head_step(r, &view, first, std::min(kHeadPredictSlab, b->n - first), b->pred + first, /*update=*/false, stream);
+        const uint32_t n = std::min(kHeadPredictSlab, b->n - first);
+        if (fused_lds && n <= kHeadFusedMaxN) {
+            LaunchRecord l{};  // (which head ran: the record of the head-input launch before it is replaced)
+            l.family = FWGPU_KERNEL_HEAD_FUSED;
+            l.threads = (int32_t)kHeadFusedThreads;
+            l.lds_bytes = (int32_t)fused_lds;
+            launched(r, l);
+            const int rc = head_forward_fused(r, r->pred_x + (size_t)first * r->nn.X, n, b->pred + first, stream);
+            if (rc) return rc;
+            continue;
+        }
+        const int rc = head_step(r, &view, first, n, b->pred + first, /*update=*/false, stream);
         if (rc) return rc;
     }
     return FWGPU_OK;
@@ -839,6 +856,22 @@ int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n) 
     if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (n > FWGPU_LAUNCH_INFO_LEN) return fail(FWGPU_ERR_RANGE, "last_launch: more fields than the library fills (FWGPU_LAUNCH_INFO_LEN)");
     for (uint32_t i = 0; i < n; i++) out[i] = r->last_launch[i];
+    return FWGPU_OK;
+}
+
+int fwgpu_enable_fused_head(fwgpu_regressor *r) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (r->packed()) return fail(FWGPU_ERR_INVALID, "enable_fused_head: a packed regressor has no deep head route");
+    if (!r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "enable_fused_head: the regressor has no deep head");
+    r->fused_head = true;
+    return FWGPU_OK;
+}
+
+int fwgpu_fused_head_state(const fwgpu_regressor *r, int *enabled, uint64_t *lds_bytes, uint64_t *lds_per_cu) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (enabled) *enabled = r->fused_head ? 1 : 0;
+    if (lds_bytes) *lds_bytes = head_fused_lds_bytes(r);
+    if (lds_per_cu) *lds_per_cu = r->lds_per_cu;
     return FWGPU_OK;
 }
 

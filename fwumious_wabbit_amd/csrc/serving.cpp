@@ -14,7 +14,8 @@
 // behind the FFM block inherits forward_with_cache): the cache also keeps how many features it holds per field, which is what the head's input diagonal
 // needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (launch.cpp run_batch_head_predict), a smaller one
 // the per-example kernel; with --head_requests on the command (fwgpu_enable_head_requests) fwgpu_predictor_predict_requests serves such a model too,
-// through the head-input kernels of requests_head.hip.  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
+// through the head-input kernels of requests_head.hip; with --fused_head (fwgpu_enable_fused_head) a batch of any size takes the batched head route and
+// small ones run the whole head in one launch (head_fused.hip).  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
 // unless the command also holds --packed_context_cache: the model's regressor then gets fwgpu_packed_enable_caches, fw_setup_cache builds the
 // device cache from the packed table (no record cover: every cached call takes the ENTRY route), and fw_predict_with_cache,
 // fwgpu_predictor_predict_batch(with_cache) and fwgpu_predictor_predict_requests score the filtered candidate against it on the requests kernels.
@@ -237,12 +238,13 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         if (words[i] == "-i" || words[i] == "--initial_regressor") weights = words[i + 1];
         if (words[i] == "--device") device = std::atoi(words[i + 1].c_str());  // ours: which GPU serves
     }
-    bool packed = false, packed_caches = false, head_requests = false;
+    bool packed = false, packed_caches = false, head_requests = false, fused_head = false;
     for (const auto &w : words) {
         if (w.rfind("--initial_regressor=", 0) == 0) weights = w.substr(std::strlen("--initial_regressor="));
         if (w == "--packed_weights") packed = true;  // ours: the FFM weights stay f16 buckets on the device (fwgpu_model_load_packed)
         if (w == "--packed_context_cache") packed_caches = true;  // ours: ... and context caches are built from them (fwgpu_packed_enable_caches)
         if (w == "--head_requests") head_requests = true;  // ours: a deep-head model takes the requests route (fwgpu_enable_head_requests)
+        if (w == "--fused_head") fused_head = true;  // ours: small batches run the whole head in one launch (fwgpu_enable_fused_head)
     }
     if (packed_caches && !packed) {
         set_error("--packed_context_cache is valid only together with --packed_weights (an f32 predictor keeps its context cache without it)");
@@ -252,14 +254,19 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         set_error("Cannot resolve input weights file name");  // the reference panics here (lib.rs:164-167)
         return nullptr;
     }
-    if (head_requests) {  // the file's header decides, before a device is touched
+    if (head_requests || fused_head) {  // the file's header decides, before a device is touched
         fwgpu_model_instance *mi = nullptr;
         fwgpu_nn_config nn{};
         if (fwgpu_model_read_header(weights.c_str(), nullptr, &mi) != FWGPU_OK) return nullptr;
         const int rc = fwgpu_mi_configs(mi, device, nullptr, nullptr, &nn);
         fwgpu_mi_free(mi);
         if (rc != FWGPU_OK) return nullptr;
-        if (nn.n_layers == 0 || packed) {
+        if (fused_head && (nn.n_layers == 0 || packed)) {
+            set_error(packed ? "--fused_head is not valid together with --packed_weights (a packed regressor has no deep head route)"
+                             : "--fused_head is valid only on a model with a deep head");
+            return nullptr;
+        }
+        if (head_requests && (nn.n_layers == 0 || packed)) {
             set_error(packed ? "--head_requests is not valid together with --packed_weights (a packed regressor has no deep head route)"
                              : "--head_requests is valid only on a model with a deep head (fwgpu_predictor_predict_requests serves a headless model without it)");
             return nullptr;
@@ -271,6 +278,7 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         return nullptr;
     if (packed_caches && fwgpu_packed_enable_caches(model->re) != FWGPU_OK) return nullptr;
     if (head_requests && fwgpu_enable_head_requests(model->re) != FWGPU_OK) return nullptr;  // (a model without a head: an error, with the reason)
+    if (fused_head && fwgpu_enable_fused_head(model->re) != FWGPU_OK) return nullptr;
     if (fwgpu_mi_configs(model->mi, device, nullptr, &model->tr, nullptr) != FWGPU_OK) return nullptr;
     auto p = std::make_unique<FfiPredictor>();
     p->model = model;

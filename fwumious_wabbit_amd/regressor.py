@@ -584,6 +584,24 @@ class Regressor:
         check(self.L.fwgpu_head_requests_state(self.h, C.byref(on)))
         return bool(on.value)
 
+    def enable_fused_head(self):
+        """one-way switch on an f32 regressor with a deep head: predict-only HOGWILD batches of any size take the batched head route, and slabs up to
+        the measured crossover run the whole head in one launch, activations in LDS (csrc/head_fused.hip) -- fwgpu_enable_fused_head"""
+        check(self.L.fwgpu_enable_fused_head(self.h))
+
+    def fused_head_state(self):
+        """(enabled, the fused kernel's LDS bytes for this head -- 0: not served, the GEMM route stays --, the CU's LDS bytes) -- fwgpu_fused_head_state"""
+        on, lds, cu = C.c_int32(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.L.fwgpu_fused_head_state(self.h, C.byref(on), C.byref(lds), C.byref(cu)))
+        return bool(on.value), lds.value, cu.value
+
+    def debug_head_forward_time(self, n, fused, reps=20):
+        """(milliseconds per pass, predictions) of the head alone over the first n head inputs the last batched head predict launch left on the device:
+        the fused kernel or the GEMM route -- fwgpu_debug_head_forward_time"""
+        ms, pred = C.c_float(0), np.empty(int(n), dtype=np.float32)
+        check(self.L.fwgpu_debug_head_forward_time(self.h, int(n), int(bool(fused)), int(reps), C.byref(ms), ptr(pred)))
+        return ms.value, pred
+
     def debug_requests_time(self, batch, rows=0, reps=20) -> float:
         """milliseconds per launch of the requests route of a batch with a set attached, by device events; rows: the packed predict kernel's rows
         in flight (4 or 8; 0 = the default) -- fwgpu_debug_requests_time"""

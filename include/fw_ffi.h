@@ -16,7 +16,9 @@
  *                                                         `--head_requests` (ours, only on a model with a deep head and
  *                                                         without --packed_weights, else an error) lets
  *                                                         fwgpu_predictor_predict_requests serve such a model
- *                                                         (fwgpu_enable_head_requests).  NULL +
+ *                                                         (fwgpu_enable_head_requests); `--fused_head` (ours, under the
+ *                                                         same two conditions) runs such a model's head in one launch for
+ *                                                         small batches (fwgpu_enable_fused_head).  NULL +
  *                                                         fwgpu_last_error() on failure (the reference panics).
  *   lib.rs:187-205  clone_lite(prototype)                 cheap per-thread copy sharing the weights
  *   lib.rs:207-212  fw_predict(ptr, vw_text)              -> prediction, or -1.0 for EOF / a line that does not parse

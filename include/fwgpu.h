@@ -603,6 +603,7 @@ int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 #define FWGPU_KERNEL_REQUESTS 4 /* the requests kernels (FWGPU_ROUTE_REQUESTS): [1] = ceil(R / 256), [6] = threads per workgroup, [7] = LDS bytes, [2]..[5] = 0 */
 #define FWGPU_KERNEL_PACKED_REQUESTS 5 /* ... their instantiation on a packed table (fwgpu_packed_enable_caches); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_KERNEL_HEAD_REQUESTS 6 /* the head-input kernels of the requests route on a model with a deep head (fwgpu_enable_head_requests); the fields as FWGPU_KERNEL_REQUESTS */
+#define FWGPU_KERNEL_HEAD_FUSED 7 /* the whole deep head in one launch (fwgpu_enable_fused_head, csrc/head_fused.hip), recorded AFTER the launch that formed the head inputs: [6] = 512, [7] = LDS bytes, the rest 0 */
 #define FWGPU_LAUNCH_INFO_LEN 8
 int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
@@ -880,6 +881,25 @@ int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *
  * (min(fields, largest FFM entry count) * F * k + F (F + 1) / 2) floats exceed the 160 KiB LDS. */
 int fwgpu_enable_head_requests(fwgpu_regressor *r);
 int fwgpu_head_requests_state(const fwgpu_regressor *r, int *enabled);
+/* ---- the deep head's predict-only forward in one launch, for small serving batches (opt-in).  fwgpu_enable_fused_head is a ONE-WAY switch on an f32
+ * regressor with a deep head; FWGPU_ERR_INVALID with the reason for a regressor without a head and for a packed regressor.  Without it nothing changes
+ * route or bits.  With it:
+ *   - a predict-only FWGPU_MODE_HOGWILD batch of ANY size >= 1 whose shape the head-input launch stages takes FWGPU_ROUTE_HEAD_BATCHED (without the
+ *     switch: 256 examples or more; below that the per-example forward, which re-reads the dense weights for every example);
+ *   - on that route and on FWGPU_ROUTE_REQUESTS of a deep-head model, a slab of at most 32 768 examples (the largest measured size at which it is the
+ *     faster one, profiles/head_fused.json -- i.e. every slab; up to 1024 examples it is slower than the GEMMs, 0.035 ms against 0.015 - 0.019 ms)
+ *     goes through head_forward_fused_kernel (csrc/head_fused.hip) in place of the per-layer GEMMs: one workgroup per 32 examples runs every hidden
+ *     layer (block_neural.rs:196-222, block_relu.rs:38-54) on v_mfma_f32_32x32x2_f32 with the activations in LDS, then the final neuron and the
+ *     sigmoid's rules.  fwgpu_debug_last_launch then reports FWGPU_KERNEL_HEAD_FUSED; fwgpu_debug_head_inputs serves x as ever.
+ * A head whose tile of 32 examples -- 32 * (8 ceil(X / 8) + 2 * 8 ceil(widest layer / 8)) floats -- exceeds the CU's LDS keeps the GEMM route.
+ * No atomics: two launches give the same bits, and a prediction does not depend on the examples it shares a launch with.
+ * fwgpu_fused_head_state: the switch, the kernel's LDS bytes for this regressor's head (0: not served), the CU's LDS (each may be NULL). */
+int fwgpu_enable_fused_head(fwgpu_regressor *r);
+int fwgpu_fused_head_state(const fwgpu_regressor *r, int *enabled, uint64_t *lds_bytes, uint64_t *lds_per_cu);
+/* debug (scripts/bench_head_fused.py): milliseconds per pass, by device events over `reps` passes on the null stream after one warm-up pass, of the
+ * head alone over the first n rows of x that the last batched head predict launch left on the device: fused != 0 the fused kernel (FWGPU_ERR_RANGE where
+ * it does not serve the head), else the GEMM route (head_step, update = false).  pred (n floats, may be NULL): the last pass's predictions. */
+int fwgpu_debug_head_forward_time(fwgpu_regressor *r, uint32_t n, int fused, uint32_t reps, float *ms_per_pass, float *pred);
 /* debug: a cache's contents as the device holds them -- T [F * F * k], dcf [F], cnt [F], the epoch it was set up at (each may be NULL).  Waits for the device. */
 int fwgpu_debug_block_cache_read(const fwgpu_block_cache *cache, float *T, float *dcf, uint32_t *cnt, uint64_t *epoch);
 /* debug (scripts/bench_serving_packed_requests.py): milliseconds per launch, by device events over `reps` launches on the null stream, of the
