@@ -353,6 +353,8 @@ static int requests_attach_single(fwgpu_batch *b, const fwgpu_block_cache *c) {
 int fwgpu_packed_enable_caches(fwgpu_regressor *r) {
     if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (!r->packed()) return fail(FWGPU_ERR_INVALID, "packed_enable_caches: the regressor's FFM weights are f32: its context caches need no switch");
+    if (r->nn.n_layers)
+        return fail(FWGPU_ERR_INVALID, "packed_enable_caches: a packed regressor with a deep head keeps no context cache (its launches form the head's inputs from the whole example)");
     r->packed_caches = true;
     return FWGPU_OK;
 }
@@ -367,7 +369,7 @@ int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *
 int fwgpu_enable_head_requests(fwgpu_regressor *r) {
     if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
     const char *why = nullptr;
-    if (r->packed()) why = "a packed regressor has no deep head route";
+    if (r->packed()) why = r->nn.n_layers ? "the deep head of a packed regressor is served from whole examples only (it keeps no context cache)" : "a packed regressor has no deep head route";
     else if (!r->nn.n_layers) why = "the regressor has no deep head: the requests route serves it without a switch";
     else if (r->cfg.ffm_k == 0) why = "the model has no FFM block";
     else if (r->cfg.ffm_k % 4 != 0) why = "ffm_k is no multiple of 4 (the requests kernel has no one-float-per-lane form)";

@@ -498,6 +498,35 @@ struct RequestsHeadParams {
 // false: one wave's slices and triangle row do not fit lds_limit bytes
 bool requests_head_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out);
 hipError_t launch_requests_head(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream);
+// ---- the head's inputs of a whole predict-only batch on a packed table (head_packed.hip; launch.cpp run_batch_packed_head)
+struct PackedHeadParams {
+    const uint16_t *ffm_q;          // the table of f16 bucket numbers ...
+    float q_increment, q_min;       // ... and its header, as the regressor holds it at the launch
+    const float *lr;                // {w, 0} pairs
+    const uint32_t *ffm_hash;       // the entry batch (CSR), as KernelParams holds it
+    const float *ffm_val;
+    const uint8_t *ffm_fld;
+    const uint32_t *ffm_off;        // [n+1]
+    const uint32_t *lr_hash;
+    const float *lr_val;
+    const uint32_t *lr_off;         // [n+1]
+    const uint16_t *lr_combo;       // combo slot of each LR entry
+    const float *label;             // [n] and importance [n]
+    const float *importance;
+    float *xbuf;                    // [n * X] the head's inputs
+    float *yi;                      // [2 n] {label, importance} where head_step reads them
+    uint32_t n, F, k, R;
+    uint32_t C, NT, X;              // combo slots, F (F + 1) / 2 triangle slots, C + NT
+    uint32_t ks, RP;                // LDS strides of a slot and of a row, in floats (PackedHeadShape)
+    int32_t has_lr;
+};
+struct PackedHeadShape {
+    uint32_t threads = 0, grid = 0, chunks = 0, ks = 0, RP = 0;
+    size_t lds_bytes = 0;
+};
+// false: the shape is not the kernel's (k % 4, rows beyond 512 floats) or the field sums do not fit lds_limit bytes
+bool packed_head_launch_shape(uint32_t F, uint32_t k, uint32_t n, uint32_t num_cus, size_t lds_limit, PackedHeadShape *out);
+hipError_t launch_packed_head_inputs(const PackedHeadParams &p, const PackedHeadShape &shape, hipStream_t stream);
 // fwgpu_setup_cache on a packed regressor (fwgpu_packed_enable_caches): the context's entries, ordered by field, -> the cache's T, dcf and cnt
 struct PackedCacheBuild {
     const uint16_t *ffm_q;
@@ -832,7 +861,8 @@ uint32_t lr_hash_mask(uint32_t bit_precision);
 uint32_t ffm_hash_mask(uint32_t ffm_bits, uint32_t ffm_k);
 void lut_init(float *lut, float learning_rate, float power_t, float init_acc);
 int refuse_packed(const fwgpu_regressor *r, const char *what);  // FWGPU_ERR_INVALID on a packed regressor, FWGPU_OK otherwise
-int create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out);
+int create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out, const fwgpu_nn_config *nn = nullptr,
+                  const float *nn_w = nullptr, uint64_t nn_w_len = 0);
 // ---- quantising a live regressor's FFM weights (model_file.cpp: the host quantiser; regressor.cpp: the device route and its callers)
 // quantization.rs:42-80 on the host: out = 8-byte header {increment, min} + n f16 bucket numbers
 void quantize_ffm(const float *w, uint64_t n, std::vector<uint8_t> &out);

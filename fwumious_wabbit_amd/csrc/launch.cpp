@@ -472,6 +472,60 @@ static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const Req
     return head_predict_slabs(r, b, stream);
 }
 
+// A packed regressor with a deep head (fwgpu_model_load_packed_head): the head's inputs of the whole batch from the buckets (head_packed.hip), then the same
+// layers.  Any batch size and both modes: the frozen weights order nothing, and there is no other route to fall to on a packed table.
+static int run_batch_packed_head(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream) {
+    static const char *kWho = "packed regressor with a deep head: ";
+    if (update) return refuse_packed(r, "an updating launch of a model with a deep head");
+    if (b->n == 0) return FWGPU_OK;
+    if (b->cache || !b->req_caches.empty()) return fail(FWGPU_ERR_INVALID, std::string(kWho) + "it keeps no context cache, the whole example is scored");
+    if (b->records) return fail(FWGPU_ERR_INVALID, std::string(kWho) + "a record batch is not served (an entry batch of the translated records is)");
+    if (b->host_copy) return fail(FWGPU_ERR_INVALID, std::string(kWho) + "an example of more than 4096 entries of a kind is not served");
+    if (!b->aligned4)
+        return fail(FWGPU_ERR_INVALID, std::string(kWho) + "an FFM entry's hash is not a multiple of 4 (rows must start where the translator's mask puts them: hash & fwgpu_ffm_hash_mask)");
+    const uint32_t F = r->cfg.ffm_num_fields, k = r->cfg.ffm_k;
+    PackedHeadShape shape;
+    if (!packed_head_launch_shape(F, k, b->n, (uint32_t)r->num_cus, r->lds_per_cu, &shape))
+        return fail(FWGPU_ERR_INVALID, std::string(kWho) + "the field sums of one example (fields x fields x ffm_k floats, padded) do not fit the CU's LDS");
+    int rc = ensure_pred_buffers(r, b, stream);
+    if (rc) return rc;
+    PackedHeadParams p{};
+    p.ffm_q = r->d_ffm_q;
+    p.q_increment = r->q_increment;
+    p.q_min = r->q_min;
+    p.lr = r->d_lr;
+    p.ffm_hash = b->ffm_hash;
+    p.ffm_val = b->ffm_val;
+    p.ffm_fld = b->ffm_fld;
+    p.ffm_off = b->ffm_off;
+    p.lr_hash = b->lr_hash;
+    p.lr_val = b->lr_val;
+    p.lr_off = b->lr_off;
+    p.lr_combo = b->lr_combo;
+    p.label = b->label;
+    p.importance = b->importance;
+    p.xbuf = r->pred_x;
+    p.yi = r->pred_yi;
+    p.n = b->n;
+    p.F = F;
+    p.k = k;
+    p.R = F * k;
+    p.C = r->cfg.num_combos;
+    p.NT = F * (F + 1) / 2;
+    p.X = r->nn.X;
+    p.ks = shape.ks;
+    p.RP = shape.RP;
+    p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
+    LaunchRecord l{};
+    l.family = FWGPU_KERNEL_PACKED_HEAD;
+    l.chunks = (int32_t)shape.chunks;
+    l.threads = (int32_t)shape.threads;
+    l.lds_bytes = (int32_t)shape.lds_bytes;
+    launched(r, l);
+    FWGPU_HIP(launch_packed_head_inputs(p, shape, stream));
+    return head_predict_slabs(r, b, stream);
+}
+
 // the fused example kernel, the deep head (if any) per example inside it
 static int run_batch_fused(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStream_t stream) {
     LaunchPlan plan;
@@ -489,6 +543,7 @@ static int run_batch_fused(fwgpu_regressor *r, fwgpu_batch *b, int mode, int upd
 // packed regressor or of a batch with a set) and, for a packed regressor, where there is nothing to launch.
 static int32_t pick_route(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update) {
     if (r->packed()) {  // fwgpu_packed_enable_caches: one cache (fwgpu_batch_set_cache) or a set
+        if (r->nn.n_layers) return FWGPU_ROUTE_PACKED_HEAD;  // (no caches on such a regressor; every n, both modes)
         return r->packed_caches && b->n && !b->req_caches.empty() ? FWGPU_ROUTE_REQUESTS : FWGPU_ROUTE_PACKED;
     }
     if (b->n == 0) return FWGPU_ROUTE_NONE;
@@ -508,6 +563,11 @@ int run_batch(fwgpu_regressor *r, fwgpu_batch *b, int mode, int update, hipStrea
         return rc;
     }
     case FWGPU_ROUTE_PACKED: return run_batch_packed(r, b, mode, update, stream);
+    case FWGPU_ROUTE_PACKED_HEAD: {
+        const int rc = run_batch_packed_head(r, b, update, stream);
+        if (route && rc == FWGPU_OK) r->pred_n = b->n;  // (x of every example is in pred_x)
+        return rc;
+    }
     case FWGPU_ROUTE_HOST_WALK: return run_batch_by_example(r, b, update, stream);
     case FWGPU_ROUTE_HEAD_BATCHED: {
         const int rc = run_batch_head_predict(r, b, stream);
@@ -861,7 +921,7 @@ int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n) 
 
 int fwgpu_enable_fused_head(fwgpu_regressor *r) {
     if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
-    if (r->packed()) return fail(FWGPU_ERR_INVALID, "enable_fused_head: a packed regressor has no deep head route");
+    if (r->packed() && !r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "enable_fused_head: a packed regressor without a deep head has no head route");
     if (!r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "enable_fused_head: the regressor has no deep head");
     r->fused_head = true;
     return FWGPU_OK;
@@ -877,7 +937,7 @@ int fwgpu_fused_head_state(const fwgpu_regressor *r, int *enabled, uint64_t *lds
 
 int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats) {
     if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
-    if ((r->last_route != FWGPU_ROUTE_HEAD_BATCHED && r->last_route != FWGPU_ROUTE_REQUESTS) || !r->pred_n || !r->pred_x)
+    if ((r->last_route != FWGPU_ROUTE_HEAD_BATCHED && r->last_route != FWGPU_ROUTE_REQUESTS && r->last_route != FWGPU_ROUTE_PACKED_HEAD) || !r->pred_n || !r->pred_x)
         return fail(FWGPU_ERR_INVALID, "head_inputs: the regressor's last batch launch was not a batched head predict");
     if (n_floats > (uint64_t)r->pred_n * r->nn.X) return fail(FWGPU_ERR_RANGE, "head_inputs: more floats than the last launch wrote (n * X)");
     FWGPU_HIP(hipDeviceSynchronize());  // (the launch may have run on a stream of the caller's)

@@ -962,7 +962,8 @@ int fwgpu_model_load(const char *path, int device, int immutable, fwgpu_vwmap **
 
 // fwgpu_model_load(immutable = 1) with the FFM weights left as f16 buckets on the device (include/fwgpu.h).  The device receives the FFM block of
 // the quantised inference file: as read when the file is one, else as quantize_ffm makes it from the file's f32 weights.
-int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, fwgpu_model_instance **mi_out, fwgpu_regressor **r_out) {
+// allow_head: fwgpu_model_load_packed_head -- a model with a deep head is served (its layers f32, head_packed.hip forms its inputs from the buckets)
+static int load_packed(const char *path, int device, fwgpu_vwmap **vw_out, fwgpu_model_instance **mi_out, fwgpu_regressor **r_out, bool allow_head) {
     if (!path || !r_out) return fail(FWGPU_ERR_INVALID, "NULL argument");
     *r_out = nullptr;
     try {
@@ -975,8 +976,8 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, 
         BlobShape s;
         int rc = shape_from_mi(mi.get(), &s);
         if (rc) return rc;
-        if (!s.nn_layer_len.empty())
-            return fail(FWGPU_ERR_INVALID, "model_load_packed: models with a deep head are not served from packed weights");
+        if (!s.nn_layer_len.empty() && !allow_head)
+            return fail(FWGPU_ERR_INVALID, "model_load_packed: models with a deep head are not served from packed weights by this call (fwgpu_model_load_packed_head serves them)");
         if (!s.ffm_len) return fail(FWGPU_ERR_INVALID, "model_load_packed: the model has no FFM block, there is nothing to pack");
         const uint64_t count = in.u64();
         if (count != s.elems())
@@ -993,6 +994,18 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, 
         std::vector<float> lr_w(s.lr_len);
         for (uint64_t i = 0; i < s.lr_len; i++) std::memcpy(&lr_w[i], src.data() + (sgd ? 4 : 8) * i, 4);  // SGD: {w}, else {w, acc}
         const uint8_t *ffm = src.data() + s.lr_len * (sgd ? 4 : 8);
+        // the deep head's layers lie behind the FFM block, f32 in every file kind (quantization.rs packs the FFM block only); a training file keeps
+        // each layer's optimizer state behind its weights (blob_body_bytes)
+        std::vector<float> nn_w;
+        {
+            const uint8_t *p = ffm + (quantized ? 8 + 2 * s.ffm_len : 4 * s.ffm_len) + (sgd ? 0 : 4 * s.ffm_len);
+            for (uint64_t len : s.nn_layer_len) {
+                const size_t at = nn_w.size();
+                nn_w.resize(at + len);
+                std::memcpy(nn_w.data() + at, p, len * 4);
+                p += len * (sgd ? 4 : 8);
+            }
+        }
         std::vector<uint8_t> q;
         if (!quantized) {
             quantize_ffm(reinterpret_cast<const float *>(ffm), s.ffm_len, q);
@@ -1000,14 +1013,16 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, 
         }
         mi->optimizer = FWGPU_OPT_SGD;  // persistence.rs:164 (immutable)
         fwgpu_config cfg;
-        rc = fwgpu_mi_configs(mi.get(), device, &cfg, nullptr, nullptr);
+        fwgpu_nn_config nn;
+        rc = fwgpu_mi_configs(mi.get(), device, &cfg, nullptr, &nn);
         if (rc) return rc;
         fwgpu_regressor *r = nullptr;
-        rc = fwgpu::create_packed(&cfg, lr_w.data(), ffm, &r);
+        rc = fwgpu::create_packed(&cfg, lr_w.data(), ffm, &r, &nn, nn_w.data(), nn_w.size());
         if (rc) return rc;
-        // a quantised inference file's weights section is what the tables hold, byte for byte: a diff of two such files patches them
+        // a quantised inference file's weights section is what the tables hold, byte for byte: a diff of two such files patches them (a head's layers
+        // behind the buckets are not the patch kernel's: no file is kept behind such a regressor, fwgpu_packed_apply_diff names the head)
         r->file_quantized_at_load = !quantized;
-        r->file_header_bytes = quantized && sgd && header_bytes > 0 ? (uint64_t)header_bytes : 0;
+        r->file_header_bytes = quantized && sgd && header_bytes > 0 && !nn.n_layers ? (uint64_t)header_bytes : 0;
         fill_views(mi.get());
         *r_out = r;
         if (vw_out) *vw_out = vw.release();
@@ -1016,6 +1031,13 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, 
     } catch (const std::exception &e) {
         return fail(FWGPU_ERR_FORMAT, e.what());
     }
+}
+
+int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw_out, fwgpu_model_instance **mi_out, fwgpu_regressor **r_out) {
+    return load_packed(path, device, vw_out, mi_out, r_out, /*allow_head=*/false);
+}
+int fwgpu_model_load_packed_head(const char *path, int device, fwgpu_vwmap **vw_out, fwgpu_model_instance **mi_out, fwgpu_regressor **r_out) {
+    return load_packed(path, device, vw_out, mi_out, r_out, /*allow_head=*/true);
 }
 
 // main.rs:136-148 --convert_inference_regressor: training file -> inference file (optimizer SGD, weights only, optional

@@ -600,6 +600,8 @@ int fwgpu_packed_apply_diff(fwgpu_regressor *r, const uint8_t *diff, uint64_t le
     if (!r || (len && !diff)) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (applied) *applied = 0;
     if (!r->packed()) return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the regressor's FFM weights are f32, not the file's f16 buckets: a byte diff of two inference files does not apply to it");
+    if (r->nn.n_layers)
+        return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the regressor has a deep head, whose layers lie behind the buckets in the file: a diff is not applied to it, load the file");
     if (r->file_quantized_at_load)
         return fail(FWGPU_ERR_INVALID, "packed_apply_diff: the regressor's file was quantised at load: its buckets are not the file's bytes");
     if (!r->file_header_bytes)

@@ -137,13 +137,15 @@ static int place_ffm_acc(fwgpu_regressor *r, size_t fbytes) {
 }
 
 static int create_impl(const fwgpu_config *cfg, bool packed, const uint8_t *packed_blob, fwgpu_regressor **out);
+static int set_nn_tables(fwgpu_regressor *r, const fwgpu_nn_config *nn);
 int fwgpu_create(const fwgpu_config *cfg, fwgpu_regressor **out) { return create_impl(cfg, false, nullptr, out); }
 
 }  // extern "C"
 
 // The packed form: `blob` is the quantised file's FFM block as it is (8-byte header {f32 increment, f32 min}, then one f16 bucket number per weight),
-// lr_w the LR weights [2^bit_precision].  Neither an f32 weight table nor an accumulator table is ever allocated.
-int fwgpu::create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out) {
+// lr_w the LR weights [2^bit_precision].  Neither an f32 weight table nor an accumulator table is ever allocated.  nn / nn_w (both or neither): the
+// deep head's configuration and its dense weights, all layers back to back in block order -- kept f32, as the quantised file keeps them.
+int fwgpu::create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8_t *blob, fwgpu_regressor **out, const fwgpu_nn_config *nn, const float *nn_w, uint64_t nn_w_len) {
     if (!cfg || !lr_w || !blob || !out) return fail(FWGPU_ERR_INVALID, "create_packed: NULL argument");
     if (cfg->optimizer != FWGPU_OPT_SGD) return fail(FWGPU_ERR_INVALID, "create_packed: a packed regressor is an immutable (SGD) one");
     if (!cfg->ffm_k) return fail(FWGPU_ERR_INVALID, "packed regressor: the model has no FFM block, there is nothing to pack");
@@ -158,6 +160,16 @@ int fwgpu::create_packed(const fwgpu_config *cfg, const float *lr_w, const uint8
     if (hipMemcpy(r->d_lr, tmp.data(), r->lr_len * 8, hipMemcpyHostToDevice) != hipSuccess) {
         fwgpu_free(r);
         return fail(FWGPU_ERR_DEVICE, "create_packed: LR upload failed");
+    }
+    if (nn && nn->n_layers) {
+        rc = nn_w ? set_nn_tables(r, nn) : fail(FWGPU_ERR_INVALID, "create_packed: a deep head without its weights");
+        if (rc == FWGPU_OK && r->nn_len != nn_w_len) rc = fail(FWGPU_ERR_FORMAT, "create_packed: the dense layers given are not the size the model's head has");
+        if (rc == FWGPU_OK && hipMemcpy(r->d_nn_w, nn_w, r->nn_len * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(FWGPU_ERR_DEVICE, "create_packed: upload of the deep head's weights failed");
+        if (rc) {
+            fwgpu_free(r);
+            return rc;
+        }
     }
     *out = r;
     return FWGPU_OK;
@@ -287,6 +299,10 @@ int fwgpu_init_weights(fwgpu_regressor *r) {
 int fwgpu_set_nn(fwgpu_regressor *r, const fwgpu_nn_config *nn) {
     if (!r || !nn) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (int rcp = refuse_packed(r, "set_nn (the deep head)")) return rcp;
+    return set_nn_tables(r, nn);
+}
+// ... and for a packed regressor at its creation (create_packed): the head's tables are the ordinary f32 ones whatever the FFM table's storage
+static int set_nn_tables(fwgpu_regressor *r, const fwgpu_nn_config *nn) {
     if (r->cfg.wiring != FWGPU_WIRING_REGRESSOR) return fail(FWGPU_ERR_INVALID, "the deep head needs the REGRESSOR wiring");
     if (nn->n_layers == 0 || nn->n_layers > FWGPU_NN_MAX_LAYERS) return fail(FWGPU_ERR_INVALID, "nn: n_layers must be in 1..8");
     if (nn->topology != 1 && nn->topology != 2)
@@ -898,7 +914,10 @@ int fwgpu_pack_regressor(fwgpu_regressor *src, fwgpu_regressor **out) {
     int rc = refuse_packed(src, "pack_regressor (the source)");
     if (rc) return rc;
     // the refusals of fwgpu_model_load_packed, in its words
-    if (src->nn.n_layers) return fail(FWGPU_ERR_INVALID, "model_load_packed: models with a deep head are not served from packed weights");
+    if (src->nn.n_layers)
+        return fail(FWGPU_ERR_INVALID, "pack_regressor: a trainer with a deep head is not packed (fwgpu_model_load_packed_head serves such a model from its file)");
+    if (*out && (*out)->nn.n_layers)
+        return fail(FWGPU_ERR_INVALID, "pack_regressor: the target is a packed regressor with a deep head: it is not refreshed in place (load the new file)");
     if (!src->ffm_len) return fail(FWGPU_ERR_INVALID, "model_load_packed: the model has no FFM block, there is nothing to pack");
     if (!packed_shape_ok(src->cfg.ffm_k, src->cfg.ffm_num_fields))
         return fail(FWGPU_ERR_INVALID, "packed regressor: ffm_k must be a multiple of 4 and a row (ffm_k x fields) at most 256 weights, or at most 512 with ffm_k dividing 256; got ffm_k = " +

@@ -193,6 +193,14 @@ float predict_line(FfiPredictor *p, const char *prefix, size_t prefix_len, const
             return kExceptionErrorCode;
         return out;
     }
+    if (m.re->packed() && m.re->nn.n_layers) {
+        // --packed_weights on a model with a deep head: the head-input kernel of the packed table takes entry batches only (head_packed.hip), so the
+        // line -- with a context, the whole context + candidate line: such a predictor keeps no cache -- is translated here and goes as a batch of one
+        float label, imp, out = kExceptionErrorCode;
+        if (translate_record(&m.tr, p->record.data(), n_words, p->lr, p->ffm, &label, &imp) != FWGPU_OK) return kExceptionErrorCode;
+        if (fwgpu_predict(m.re, p->lr.data(), (uint32_t)p->lr.size(), p->ffm.data(), (uint32_t)p->ffm.size(), &out) != FWGPU_OK) return kExceptionErrorCode;
+        return out;
+    }
     // The request goes into host memory the device has mapped; the kernel reads it over PCIe in its stage phase and writes the
     // prediction back the same way.  Per call: one kernel launch and one synchronisation (before: two copies in, a memset, the
     // launch, a copy out and the synchronisation).
@@ -261,19 +269,19 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         const int rc = fwgpu_mi_configs(mi, device, nullptr, nullptr, &nn);
         fwgpu_mi_free(mi);
         if (rc != FWGPU_OK) return nullptr;
-        if (fused_head && (nn.n_layers == 0 || packed)) {
-            set_error(packed ? "--fused_head is not valid together with --packed_weights (a packed regressor has no deep head route)"
+        if (fused_head && nn.n_layers == 0) {
+            set_error(packed ? "--fused_head is not valid together with --packed_weights on a model without a deep head (a packed regressor has no head route for it)"
                              : "--fused_head is valid only on a model with a deep head");
             return nullptr;
         }
         if (head_requests && (nn.n_layers == 0 || packed)) {
-            set_error(packed ? "--head_requests is not valid together with --packed_weights (a packed regressor has no deep head route)"
+            set_error(packed ? "--head_requests is not valid together with --packed_weights (a packed regressor keeps no context cache for a deep head)"
                              : "--head_requests is valid only on a model with a deep head (fwgpu_predictor_predict_requests serves a headless model without it)");
             return nullptr;
         }
     }
     auto model = std::make_shared<SharedModel>();
-    if ((packed ? fwgpu_model_load_packed(weights.c_str(), device, &model->vw, &model->mi, &model->re)
+    if ((packed ? fwgpu_model_load_packed_head(weights.c_str(), device, &model->vw, &model->mi, &model->re)
                 : fwgpu_model_load(weights.c_str(), device, /*immutable=*/1, &model->vw, &model->mi, &model->re)) != FWGPU_OK)
         return nullptr;
     if (packed_caches && fwgpu_packed_enable_caches(model->re) != FWGPU_OK) return nullptr;
@@ -365,6 +373,9 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
     // records + the kernel's own translation, unless a candidate turns out to need the entry route (FWGPU_SERVING_ENTRY_ROUTE=1 forces that one)
     // (--packed_context_cache: the entry route always -- a packed regressor's cache knows no record)
     bool by_record = cached && !m.re->packed() && !std::getenv("FWGPU_SERVING_ENTRY_ROUTE");
+    // --packed_weights on a model with a deep head: the head-input kernel of the packed table takes entry batches only (head_packed.hip), so every line
+    // is translated here, whole, and nothing is filtered (such a predictor keeps no context cache)
+    const bool whole_entries = m.re->packed() && m.re->nn.n_layers != 0;
     // ... and of those records only what the candidate adds to the context's record, which the device already holds
     // (FWGPU_SERVING_MERGED_RECORDS=1: whole context + candidate records instead)
     const bool delta_wanted = ptr->delta_ok && !std::getenv("FWGPU_SERVING_MERGED_RECORDS");
@@ -418,11 +429,11 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
                 pt.entry_route = true;
                 break;  // the whole request goes again, by entries
             }
-            if (cached && !by_record) {
+            if ((cached && !by_record) || whole_entries) {
                 float label, imp;
                 if (translate_record(&m.tr, rec.data(), nw, t_lr, t_ffm, &label, &imp) != FWGPU_OK) continue;
-                uint32_t kept = 0;
-                if (fwgpu_block_cache_filter(ptr->cache, t_ffm.data(), (uint32_t)t_ffm.size(), t_ffm.data(), &kept) != FWGPU_OK) continue;
+                uint32_t kept = (uint32_t)t_ffm.size();
+                if (cached && fwgpu_block_cache_filter(ptr->cache, t_ffm.data(), (uint32_t)t_ffm.size(), t_ffm.data(), &kept) != FWGPU_OK) continue;
                 if (append_example(m.re, pt.hb, t_lr.data(), (uint32_t)t_lr.size(), t_ffm.data(), kept, 0.0f, 1.0f) != FWGPU_OK) {
                     pt.hb_ok = false;
                     continue;
@@ -477,7 +488,7 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
     if (slot.empty()) return FWGPU_OK;
     std::lock_guard<std::mutex> g(m.mu);
     const uint32_t nrec = (uint32_t)slot.size();
-    if (cached && !by_record) {  // one entry batch, every example starting from the cached field sums
+    if ((cached && !by_record) || whole_entries) {  // one entry batch, every example starting from the cached field sums (whole_entries: from nothing)
         HostBatch hb;
         hb.clear();
         {   // the parts' SoA arrays land in one host batch at their offsets (copied by one thread per part), example offsets rebased
@@ -528,8 +539,8 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
         int rc0 = batch_alloc(m.re, nrec, hb.lr_hash.size(), hb.ffm_hash.size(), &eb);
         if (rc0 != FWGPU_OK) return rc0;
         rc0 = batch_upload(eb, hb, 0);
-        if (rc0 == FWGPU_OK) rc0 = refresh_stale_cache(ptr);
-        if (rc0 == FWGPU_OK) rc0 = fwgpu_batch_set_cache(eb, ptr->cache);
+        if (rc0 == FWGPU_OK && cached) rc0 = refresh_stale_cache(ptr);
+        if (rc0 == FWGPU_OK && cached) rc0 = fwgpu_batch_set_cache(eb, ptr->cache);
         if (rc0 == FWGPU_OK) rc0 = fwgpu_learn_batch(m.re, eb, FWGPU_MODE_HOGWILD, /*update=*/0, nullptr);
         std::vector<float> preds(nrec);
         if (rc0 == FWGPU_OK) rc0 = fwgpu_batch_predictions(eb, preds.data(), nrec, nullptr);
@@ -614,7 +625,8 @@ int fwgpu_predictor_predict_text(FfiPredictor *ptr, const char *text, uint64_t l
     if (len == 0) return FWGPU_OK;
     SharedModel &m = *ptr->model;
     const bool cand = with_cache != 0;
-    if (std::getenv("FWGPU_SERVING_HOST_PARSE") || (cand && !(ptr->cache && ptr->prefix && ptr->delta_ok)))
+    // (--packed_weights on a model with a deep head: entry batches only -- fwgpu_predictor_predict_batch translates the lines)
+    if (std::getenv("FWGPU_SERVING_HOST_PARSE") || (cand && !(ptr->cache && ptr->prefix && ptr->delta_ok)) || (m.re->packed() && m.re->nn.n_layers))
         return predict_text_by_lines(ptr, text, len, with_cache, out, cap, n);
     std::string owned;
     if (text[len - 1] != '\n') {  // the last line gets its newline, as every line a caller of fw_predict sends has one

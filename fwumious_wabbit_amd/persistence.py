@@ -127,16 +127,21 @@ def load_regressor_without_weights(filename: str):
     return ModelInstanceHandle(mi), VwNamespaceMap(_handle=vw)
 
 
-def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0, packed: bool = False, packed_caches: bool = False):
+def new_regressor_from_filename(filename: str, immutable: bool, device: int = 0, packed: bool = False, packed_caches: bool = False,
+                                packed_head: bool = False):
     """persistence.rs:127-174 -> (ModelInstance, VwNamespaceMap, Regressor).  packed: an immutable regressor whose FFM weights stay the
-    quantised file's f16 buckets in device memory (fwgpu_model_load_packed): half the table, predict-only.  packed_caches (with packed only):
+    quantised file's f16 buckets in device memory (fwgpu_model_load_packed): half the table, predict-only.  packed_head (with packed only): a model with a deep head is accepted too, its layers kept f32 and its
+    launches forming the head's inputs from the buckets (fwgpu_model_load_packed_head); without it such a model is refused.  packed_caches (with packed only):
     the regressor also keeps context caches (Regressor.enable_packed_caches)"""
     if packed_caches and not packed:
         raise ValueError("packed_caches needs packed=True")
     L = capi.lib()
     vw, mih, r = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    if packed_head and not packed:
+        raise ValueError("packed_head needs packed=True")
     if packed:
-        capi.check(L.fwgpu_model_load_packed(filename.encode(), device, C.byref(vw), C.byref(mih), C.byref(r)))
+        load = L.fwgpu_model_load_packed_head if packed_head else L.fwgpu_model_load_packed
+        capi.check(load(filename.encode(), device, C.byref(vw), C.byref(mih), C.byref(r)))
     else:
         capi.check(L.fwgpu_model_load(filename.encode(), device, int(immutable), C.byref(vw), C.byref(mih), C.byref(r)))
     h = ModelInstanceHandle(mih)

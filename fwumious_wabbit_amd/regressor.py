@@ -585,7 +585,7 @@ class Regressor:
         return bool(on.value)
 
     def enable_fused_head(self):
-        """one-way switch on an f32 regressor with a deep head: predict-only HOGWILD batches of any size take the batched head route, and slabs up to
+        """one-way switch on a regressor with a deep head (f32 or packed): predict-only HOGWILD batches of any size take the batched head route, and slabs up to
         the measured crossover run the whole head in one launch, activations in LDS (csrc/head_fused.hip) -- fwgpu_enable_fused_head"""
         check(self.L.fwgpu_enable_fused_head(self.h))
 

@@ -587,6 +587,8 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value);
 #define FWGPU_ROUTE_PACKED 4               /* packed regressor: the packed predict kernel (or its refusal) */
 #define FWGPU_ROUTE_HOST_WALK 5            /* a batch with an oversize example: walked example by example from its host copy */
 #define FWGPU_ROUTE_REQUESTS 6             /* predict-only entry batch with a cache per example (fwgpu_batch_set_caches) */
+#define FWGPU_ROUTE_PACKED_HEAD 7          /* packed regressor with a deep head: head inputs from the buckets for the whole batch (csrc/head_packed.hip), layers as on
+                                              FWGPU_ROUTE_HEAD_BATCHED; any n >= 1, both modes, entry batches only (or its refusal) */
 int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 /* What the regressor's last example-kernel launch ran, from its RESOLVED launch parameters (host side, read-only; every batch launch that reaches the
  * example kernel records it, the launch of a refused batch does not): the first n <= FWGPU_LAUNCH_INFO_LEN of
@@ -604,10 +606,11 @@ int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 #define FWGPU_KERNEL_PACKED_REQUESTS 5 /* ... their instantiation on a packed table (fwgpu_packed_enable_caches); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_KERNEL_HEAD_REQUESTS 6 /* the head-input kernels of the requests route on a model with a deep head (fwgpu_enable_head_requests); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_KERNEL_HEAD_FUSED 7 /* the whole deep head in one launch (fwgpu_enable_fused_head, csrc/head_fused.hip), recorded AFTER the launch that formed the head inputs: [6] = 512, [7] = LDS bytes, the rest 0 */
+#define FWGPU_KERNEL_PACKED_HEAD 8 /* the head-input kernel of a packed regressor with a deep head (FWGPU_ROUTE_PACKED_HEAD): [1] = ceil(R / 256), [6] = 256, [7] = LDS bytes, [2]..[5] = 0 */
 #define FWGPU_LAUNCH_INFO_LEN 8
 int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
- * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED
+ * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED, FWGPU_ROUTE_PACKED_HEAD
  * or, on a model with a deep head, FWGPU_ROUTE_REQUESTS (fwgpu_enable_head_requests); FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */
 int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats);
 /* an f32 as serde_json / ryu prints it in the embedded JSON documents ("0.1", "1.0", "1e-7"); NUL-terminated */
@@ -845,11 +848,20 @@ int fwgpu_model_load(const char *path, int device, int immutable, fwgpu_vwmap **
  * train -- update != 0, fwgpu_learn_batch_sync, fwgpu_table_write / fill / device_ptr on the FFM tables, fwgpu_read_weights,
  * fwgpu_write_weights, fwgpu_model_save, fwgpu_trainer_create, fwgpu_dist_*, hogwild_load into it -- and fwgpu_setup_cache
  * (unless fwgpu_packed_enable_caches was called, below) return FWGPU_ERR_INVALID and leave it usable.
- * Refused here with FWGPU_ERR_INVALID: models with a deep head, models without an FFM block, ffm_k % 4 != 0, rows
+ * Refused here with FWGPU_ERR_INVALID: models without an FFM block, ffm_k % 4 != 0, rows
  * (ffm_k x fields) of more than 256 weights unless ffm_k divides 256 and the row has at most 512.  Refused at the launch:
  * entry batches with an FFM hash that is not a multiple of 4 (raw entries that did not pass fwgpu_ffm_hash_mask), examples
- * of more than 2048 FFM features. */
+ * of more than 2048 FFM features.
+ * A model with a deep head is refused by this call, as ever (fwgpu_model_load_packed_head below serves it). */
 int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw, fwgpu_model_instance **mi, fwgpu_regressor **r);
+/* fwgpu_model_load_packed that also accepts a model with a DEEP HEAD (and is that call for a model without one), from the same three
+ * file kinds: LR stays {w, 0} pairs, the FFM block goes to buckets as above, the layers behind it are read as f32 into the ordinary
+ * head tables (FWGPU_TABLE_NN_W is bit for bit the f32 load's).  Every predict-only launch of an ENTRY batch on such a regressor, of
+ * any size and in both modes, takes FWGPU_ROUTE_PACKED_HEAD (csrc/head_packed.hip forms the head's inputs from the buckets, then the
+ * layers; fwgpu_enable_fused_head is accepted).  On it record batches, fwgpu_pack_regressor (from or into it),
+ * fwgpu_packed_apply_diff, fwgpu_packed_enable_caches and fwgpu_enable_head_requests return FWGPU_ERR_INVALID with a message that
+ * names the head, as does a shape whose field sums do not fit the CU's LDS.  The shapes refused at the load are those above. */
+int fwgpu_model_load_packed_head(const char *path, int device, fwgpu_vwmap **vw, fwgpu_model_instance **mi, fwgpu_regressor **r);
 /* How the FFM weight table lives on the device, and the bytes it occupies there */
 enum { FWGPU_FFM_F32 = 0, FWGPU_FFM_F16_BUCKETS = 1 };
 int fwgpu_ffm_storage(fwgpu_regressor *r, int *storage, uint64_t *table_bytes);
@@ -881,9 +893,9 @@ int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *
  * (min(fields, largest FFM entry count) * F * k + F (F + 1) / 2) floats exceed the 160 KiB LDS. */
 int fwgpu_enable_head_requests(fwgpu_regressor *r);
 int fwgpu_head_requests_state(const fwgpu_regressor *r, int *enabled);
-/* ---- the deep head's predict-only forward in one launch, for small serving batches (opt-in).  fwgpu_enable_fused_head is a ONE-WAY switch on an f32
- * regressor with a deep head; FWGPU_ERR_INVALID with the reason for a regressor without a head and for a packed regressor.  Without it nothing changes
- * route or bits.  With it:
+/* ---- the deep head's predict-only forward in one launch, for small serving batches (opt-in).  fwgpu_enable_fused_head is a ONE-WAY switch on a
+ * regressor with a deep head, whether its FFM table is f32 or packed (fwgpu_model_load_packed_head: the head's own tables are f32 either way);
+ * FWGPU_ERR_INVALID with the reason for a regressor without a head.  Without it nothing changes route or bits.  With it:
  *   - a predict-only FWGPU_MODE_HOGWILD batch of ANY size >= 1 whose shape the head-input launch stages takes FWGPU_ROUTE_HEAD_BATCHED (without the
  *     switch: 256 examples or more; below that the per-example forward, which re-reads the dense weights for every example);
  *   - on that route and on FWGPU_ROUTE_REQUESTS of a deep-head model, a slab of at most 32 768 examples (the largest measured size at which it is the
