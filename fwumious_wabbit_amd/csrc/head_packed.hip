@@ -1,7 +1,7 @@
 // The head's inputs of a whole predict-only batch on a PACKED table (fwgpu_model_load_packed_head of a model with a deep head; DESIGN.md 4.8 "Deep heads").
 //
-// x = [C per-combo LR sums | NT = F (F + 1) / 2 triangle slots], slot t = i (i + 1) / 2 + j, j <= i -- the x of kernels.hip's emit_x branch, restated at
-// the top of requests_head.hip.  With S_f the R-vector of field f's sum of v * row over the example's entries of field f (S_f[z] its k floats facing z):
+// x = [C per-combo LR sums | NT = F (F + 1) / 2 triangle slots], slot t = i (i + 1) / 2 + j, j <= i -- the x of kernels.hip's emit_x branch (its formulas: the
+// top of requests_head.hip; t -> (i, j): tri_slot).  With S_f the R-vector of field f's sum of v * row over the example's entries of field f (S_f[z] its k floats facing z):
 //
 //     (i, j), j < i:  <S_i[j], S_j[i]>
 //     (f, f):         +0.0 when field f has at most one entry, else 0.5 (|S_f[f]|^2 - sum_entries v^2 |w[f]|^2)
@@ -13,11 +13,11 @@
 //            runs, none) and takes them four at a time.  The lane map is that of requests.hip: lane l of chunk c holds the four weights at
 //            e0 = (c * 64 + l) * 4, facing field z = e0 / k, ONE 8-byte load of four f16 buckets predicated on e0 < R (rows start on multiples of 4
 //            buckets: the launch refuses an entry batch that is not aligned so).  All loads of the four rows are issued, then converted --
-//            kernels.hip packed_weight, restated: f16 -> f32 exactly, one multiply, one add, unfused -- and v * w is added into one (R <= 256) or two
+//            packed_weights4: f16 -> f32 exactly, one multiply, one add, unfused -- and v * w is added into one (R <= 256) or two
 //            (R <= 512) float4 per lane in entry order.  The lanes of the own slot (z == f) also add sum (v w)^2 over their four floats.  The wave
 //            stores S_f ONCE into LDS (zeros where the field has no entry), the own-slot lanes their partial self terms, lane 0 the entry count.
 //            No atomics, no two waves on one row: the bits of x do not depend on scheduling.
-//   COMBOS   the last wave (it owns the fewest fields), as requests_head_kernel: one lane per combo, the products of 64 entries at a time handed
+//   COMBOS   the last wave (it owns the fewest fields), head_combo_slots: one lane per combo, the products of 64 entries at a time handed
 //            round in buffer order.
 //   TRIANGLE after ONE workgroup barrier thread t owns slots t, t + 256, ...: its k-long dot from LDS, kk in order, every operation rounded (the build
 //            has no contraction); the diagonal by the counts; the store to xbuf[ex X + C + t] is coalesced as it is, so no triangle row is kept
@@ -34,7 +34,7 @@
 
 #include <algorithm>
 
-#include "fwgpu_internal.h"
+#include "fwgpu_device.h"
 
 namespace fwgpu {
 
@@ -42,16 +42,6 @@ static constexpr uint32_t kPhThreads = 256;
 static constexpr uint32_t kPhWaves = kPhThreads / 64;
 static constexpr int kPhRows = 4;           // rows of a field in flight per lane
 static constexpr uint32_t kPhMaxPerCu = 8;  // workgroups per CU the grid is sized for (32 waves), where the LDS lets them in
-
-// kernels.hip packed_weight / packed_weights4, restated: the bucket's f16 pattern to f32 exactly, then ONE multiply and ONE add, unfused
-__device__ __forceinline__ float ph_packed_weight(uint32_t bucket16, float increment, float mn) {
-    const _Float16 h = __builtin_bit_cast(_Float16, (unsigned short)bucket16);
-    return __fadd_rn(mn, __fmul_rn((float)h, increment));
-}
-__device__ __forceinline__ float4 ph_packed_weights4(uint2 raw, float increment, float mn) {
-    return make_float4(ph_packed_weight(raw.x & 0xffffu, increment, mn), ph_packed_weight(raw.x >> 16, increment, mn),
-                       ph_packed_weight(raw.y & 0xffffu, increment, mn), ph_packed_weight(raw.y >> 16, increment, mn));
-}
 
 // CH: chunks of 256 floats per row (1: R <= 256, 2: R <= 512)
 template <int CH>
@@ -115,14 +105,14 @@ __global__ __launch_bounds__(kPhThreads) void packed_head_inputs_kernel(const Pa
                         if (u < live) {
 #pragma unroll
                             for (int c = 0; c < CH; ++c) {
-                                const float4 w = ph_packed_weights4(raw[c][u], p.q_increment, p.q_min);
+                                const float4 w = packed_weights4(raw[c][u], p.q_increment, p.q_min);
                                 const float4 t = make_float4(__fmul_rn(w.x, v[u]), __fmul_rn(w.y, v[u]), __fmul_rn(w.z, v[u]), __fmul_rn(w.w, v[u]));
                                 acc[c].x = __fadd_rn(acc[c].x, t.x);
                                 acc[c].y = __fadd_rn(acc[c].y, t.y);
                                 acc[c].z = __fadd_rn(acc[c].z, t.z);
                                 acc[c].w = __fadd_rn(acc[c].w, t.w);
                                 if (zf[c] == f)
-                                    fd[c] = __fadd_rn(fd[c], __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(t.x, t.x), __fmul_rn(t.y, t.y)), __fmul_rn(t.z, t.z)), __fmul_rn(t.w, t.w)));
+                                    fd[c] = __fadd_rn(fd[c], dot4(t, t));
                             }
                         }
                     }
@@ -139,33 +129,13 @@ __global__ __launch_bounds__(kPhThreads) void packed_head_inputs_kernel(const Pa
         }
         float *x = p.xbuf + (size_t)ex * p.X;
         if (wave == kPhWaves - 1) {
-            // combo slots: lane l owns combo cb + l; the products of 64 entries at a time are formed once and handed round in buffer order
-            const uint32_t l0 = p.lr_off[ex], l1 = p.has_lr ? p.lr_off[ex + 1] : l0;
-            for (uint32_t cb = 0; cb < p.C; cb += 64u) {
-                float a = 0.0f;
-                for (uint32_t b0 = l0; b0 < l1; b0 += 64u) {
-                    const uint32_t i = b0 + lane, nb = l1 - b0 < 64u ? l1 - b0 : 64u;
-                    const float prod = i < l1 ? __fmul_rn(p.lr[2ull * p.lr_hash[i]], p.lr_val[i]) : 0.0f;
-                    const uint32_t combo = i < l1 ? (uint32_t)p.lr_combo[i] : 0xffffffffu;
-                    for (uint32_t j = 0; j < nb; ++j) {
-                        const float pj = __shfl(prod, (int)j, 64);
-                        const uint32_t cj = (uint32_t)__shfl((int)combo, (int)j, 64);
-                        if (cj == cb + lane) a = __fadd_rn(a, pj);
-                    }
-                }
-                if (cb + lane < p.C) x[cb + lane] = a;
-            }
+            head_combo_slots(x, p.C, p.lr, p.lr_hash, p.lr_val, p.lr_combo, p.lr_off[ex], p.has_lr ? p.lr_off[ex + 1] : p.lr_off[ex], lane);
         }
-        if (tid == 0) {
-            p.yi[2 * (size_t)ex] = p.label[ex];
-            p.yi[2 * (size_t)ex + 1] = p.importance[ex];
-        }
+        if (tid == 0) store_label_importance(p.yi, p.label, p.importance, ex);
         __syncthreads();  // every S row, self term and count of this example is in LDS
         for (uint32_t t = tid; t < p.NT; t += kPhThreads) {
-            uint32_t i = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-            while ((i + 1) * (i + 2) / 2 <= t) ++i;
-            while (i * (i + 1) / 2 > t) --i;
-            const uint32_t j = t - i * (i + 1) / 2;
+            const uint2 ij = tri_slot(t);
+            const uint32_t i = ij.x, j = ij.y;
             const float4 *a = reinterpret_cast<const float4 *>(S + (size_t)i * RP + j * ks);  // S_i[j]
             const float4 *b = reinterpret_cast<const float4 *>(S + (size_t)j * RP + i * ks);  // S_j[i]
             float d = 0.0f;

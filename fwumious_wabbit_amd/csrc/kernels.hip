@@ -85,15 +85,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, ui
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
 }
 
-// ---- packed FFM rows (fwgpu_model_load_packed): the table holds the quantised inference file's f16 BUCKET NUMBERS, two bytes per weight, and a
-// predict-only gather turns each into the weight the host's dequantize_ffm (model_file.cpp, quantization.rs:82-98) would have stored:
-// w = min + f32(bucket) * increment -- the conversion is exact, then ONE multiply and ONE add, unfused (bit-identical for every f16 pattern).
-__device__ __forceinline__ float packed_weight(uint32_t bucket16, float increment, float mn) {
-    const _Float16 h = __builtin_bit_cast(_Float16, (unsigned short)bucket16);
-    return __fadd_rn(mn, __fmul_rn((float)h, increment));
-}
+// ---- packed FFM rows (fwgpu_model_load_packed): fwgpu_device.h packed_weight; here in the vector types of the raw buffer loads
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-// four consecutive buckets (8 bytes) -> the lane's four weights of a row
 __device__ __forceinline__ f4 packed_weights4(u2 raw, float increment, float mn) {
     return f4{packed_weight(raw[0] & 0xffffu, increment, mn), packed_weight(raw[0] >> 16, increment, mn),
               packed_weight(raw[1] & 0xffffu, increment, mn), packed_weight(raw[1] >> 16, increment, mn)};
@@ -137,14 +130,6 @@ struct Vec<1> {
     static __device__ __forceinline__ float get(const float &v, int) { return v; }
     static __device__ __forceinline__ void set(float &v, int, float x) { v = x; }
 };
-
-__device__ __forceinline__ float logistic(float t) { return 1.0f / (1.0f + expf(-t)); }  // block_loss_functions.rs:15-17
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 template <bool COH, bool SYS = false>
 __device__ __forceinline__ float2 lr_load(const float *lr, uint32_t h) {
@@ -913,10 +898,8 @@ __device__ __forceinline__ float nn_forward(const KernelParams &p, const Lds &s,
     }
     const uint32_t T = F * (F + 1) / 2;
     for (uint32_t t = tid; t < T; t += bd) {
-        uint32_t i = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-        while ((i + 1) * (i + 2) / 2 <= t) ++i;
-        while (i * (i + 1) / 2 > t) --i;
-        const uint32_t j = t - i * (i + 1) / 2;
+        const uint2 ij = tri_slot(t);
+        const uint32_t i = ij.x, j = ij.y;
         float dot = 0.0f;
         if (i != j) {
             for (uint32_t kk = 0; kk < k; ++kk) dot += s.T[i * R + j * k + kk] * s.T[j * R + i * k + kk];
@@ -2131,7 +2114,7 @@ __global__ void __launch_bounds__(1024) fw_example_kernel(const KernelParams /* 
         if (NN && p.nn.n_layers) wsum = nn_forward<VEC, COH>(p, s, nl, tid, bd);
 
         // ---------------- sigmoid / log-loss gradient (block_loss_functions.rs:105-153)
-        if (isnan(wsum)) {
+        if (isnan(wsum)) {  // (clipped_prediction, open-coded: the ladder also decides the gradient)
             pr = logistic(0.0f);
             g = 0.0f;
         } else if (wsum < -50.0f) {
@@ -2633,10 +2616,8 @@ __global__ void __launch_bounds__(256) split_mid_kernel(const KernelParams p, ui
             for (uint32_t c = tid; c < C; c += 256) x[c] = lrs[c];
             const uint32_t NT = F * (F + 1) / 2;
             for (uint32_t t = tid; t < NT; t += 256) {
-                uint32_t i = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-                while ((i + 1) * (i + 2) / 2 <= t) ++i;
-                while (i * (i + 1) / 2 > t) --i;
-                const uint32_t j = t - i * (i + 1) / 2;
+                const uint2 ij = tri_slot(t);
+                const uint32_t i = ij.x, j = ij.y;
                 float dot = 0.0f;
                 for (uint32_t kk = 0; kk < k; ++kk) dot += T[i * R + j * k + kk] * T[j * R + i * k + kk];
                 if (i == j) dot = cnt[i] <= 1.0f ? 0.0f : 0.5f * (dot - dcf[i]);
@@ -2665,7 +2646,7 @@ __global__ void __launch_bounds__(256) split_mid_kernel(const KernelParams p, ui
             if (p.has_lr) wsum += lrs[0];
             if (k) wsum += 0.5f * (dot_t - dc_t);
             float pr, g;
-            if (isnan(wsum)) {
+            if (isnan(wsum)) {  // (clipped_prediction, open-coded: the ladder also decides the gradient)
                 pr = logistic(0.0f);
                 g = 0.0f;
             } else if (wsum < -50.0f) {
@@ -3347,10 +3328,8 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
             }
             const uint32_t NT = F * (F + 1) / 2;
             for (uint32_t t = tid; t < NT; t += bd) {
-                uint32_t i = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-                while ((i + 1) * (i + 2) / 2 <= t) ++i;
-                while (i * (i + 1) / 2 > t) --i;
-                const uint32_t j = t - i * (i + 1) / 2;
+                const uint2 ij = tri_slot(t);
+                const uint32_t i = ij.x, j = ij.y;
                 float d = 0.0f;
                 for (uint32_t kk = 0; kk < k; ++kk) d += s.T[i * R + j * k + kk] * s.T[j * R + i * k + kk];
                 // the diagonal as split_mid_kernel forms it: exactly 0 for a field of at most one feature, 0.5 (|field sum|^2 - sum of the features' own squares) otherwise
@@ -3379,7 +3358,7 @@ __global__ void __launch_bounds__(NN ? FW_NN_THREADS : FW_LB_THREADS, NC == 1 ? 
 
         const float label = __uint_as_float(s.ctr[kCtrLabel]), imp = __uint_as_float(s.ctr[kCtrImp]);  // (parked by the stage phase)
         float pr, g;
-        if (isnan(wsum)) {
+        if (isnan(wsum)) {  // (clipped_prediction, open-coded: the ladder also decides the gradient)
             pr = logistic(0.0f);
             g = 0.0f;
         } else if (wsum < -50.0f) {

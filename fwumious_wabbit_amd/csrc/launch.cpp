@@ -257,6 +257,15 @@ static void launched(fwgpu_regressor *r, const LaunchRecord &l) {
     static_assert(sizeof(fields) == sizeof(r->last_launch), "fwgpu_debug_last_launch: FWGPU_LAUNCH_INFO_LEN fields");
     for (int i = 0; i < 8; i++) r->last_launch[i] = fields[i];
 }
+// ... for a launch of a serving kernel, whose shape the kernel's own file chose (requests_launch_shape and its kin)
+static void launched_shape(fwgpu_regressor *r, int family, uint32_t chunks, uint32_t threads, size_t lds_bytes) {
+    LaunchRecord l{};
+    l.family = family;
+    l.chunks = (int32_t)chunks;
+    l.threads = (int32_t)threads;
+    l.lds_bytes = (int32_t)lds_bytes;
+    launched(r, l);
+}
 // ... for a launch of the example kernels: the RESOLVED parameters (after plan_launch / resolve_row_mode)
 static void record_launch(fwgpu_regressor *r, const LaunchPlan &plan, bool packed, int optimizer) {
     const KernelParams &p = plan.p;
@@ -361,12 +370,7 @@ static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hi
     p.slots = shape.slots;
     p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
     if (head) return run_batch_head_requests(r, b, p, stream);
-    LaunchRecord l{};
-    l.family = r->packed() ? FWGPU_KERNEL_PACKED_REQUESTS : FWGPU_KERNEL_REQUESTS;
-    l.chunks = (int32_t)shape.chunks;
-    l.threads = (int32_t)shape.threads;
-    l.lds_bytes = (int32_t)shape.lds_bytes;
-    launched(r, l);
+    launched_shape(r, r->packed() ? FWGPU_KERNEL_PACKED_REQUESTS : FWGPU_KERNEL_REQUESTS, shape.chunks, shape.threads, shape.lds_bytes);
     FWGPU_HIP(launch_requests(p, shape, stream, rows));
     return FWGPU_OK;
 }
@@ -462,12 +466,7 @@ static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const Req
     p.C = r->cfg.num_combos;
     p.NT = q.F * (q.F + 1) / 2;
     p.X = r->nn.X;
-    LaunchRecord l{};
-    l.family = FWGPU_KERNEL_HEAD_REQUESTS;
-    l.chunks = (int32_t)shape.chunks;
-    l.threads = (int32_t)shape.threads;
-    l.lds_bytes = (int32_t)shape.lds_bytes;
-    launched(r, l);
+    launched_shape(r, FWGPU_KERNEL_HEAD_REQUESTS, shape.chunks, shape.threads, shape.lds_bytes);
     FWGPU_HIP(launch_requests_head(p, shape, stream));
     return head_predict_slabs(r, b, stream);
 }
@@ -516,12 +515,7 @@ static int run_batch_packed_head(fwgpu_regressor *r, fwgpu_batch *b, int update,
     p.ks = shape.ks;
     p.RP = shape.RP;
     p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
-    LaunchRecord l{};
-    l.family = FWGPU_KERNEL_PACKED_HEAD;
-    l.chunks = (int32_t)shape.chunks;
-    l.threads = (int32_t)shape.threads;
-    l.lds_bytes = (int32_t)shape.lds_bytes;
-    launched(r, l);
+    launched_shape(r, FWGPU_KERNEL_PACKED_HEAD, shape.chunks, shape.threads, shape.lds_bytes);
     FWGPU_HIP(launch_packed_head_inputs(p, shape, stream));
     return head_predict_slabs(r, b, stream);
 }

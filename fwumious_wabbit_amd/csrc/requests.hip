@@ -20,7 +20,7 @@
 // LDS per wave: min(F, the batch's largest FFM entry count) * R floats.  The waves per workgroup are chosen on the host (requests_launch_shape).
 //
 // PACKED TABLES (fwgpu_packed_enable_caches).  requests_predict_kernel is a template over the table's storage: PK = true reads a lane's four weights
-// as ONE 8-byte load of four f16 bucket numbers (rows start on a multiple of 4 buckets) and converts them as kernels.hip packed_weight does, bit for
+// as ONE 8-byte load of four f16 bucket numbers (rows start on a multiple of 4 buckets) and converts them by packed_weights4 (fwgpu_device.h), bit for
 // bit: f16 -> f32 exactly, then one multiply and one add, unfused, w = min + f32(bucket) * increment, the two header words being launch constants.
 // Everything behind the load is the f32 code.  requests_base_kernel reads caches only and serves both.
 // packed_cache_build_kernel  fwgpu_setup_cache on such a regressor: ONE wavefront per field f, the lane map of the predict kernel (chunk c, lane l:
@@ -38,7 +38,7 @@
 
 #include <algorithm>
 
-#include "fwgpu_internal.h"
+#include "fwgpu_device.h"
 
 namespace fwgpu {
 
@@ -47,29 +47,6 @@ static constexpr uint32_t kReqMaxWaves = 4;            // waves (= candidates) p
 static constexpr size_t kReqLdsTarget = 64 * 1024;     // ... as many as keep the workgroup at or below this, so several workgroups share a CU
 static constexpr int kReqRows = 4;                     // rows of a field in flight per lane
 static constexpr int kReqRowsPacked = 4;               // ... on a packed table (half the bytes per row; 4 against 8: DESIGN.md 4.8)
-
-__device__ __forceinline__ float req_logistic(float t) { return 1.0f / (1.0f + expf(-t)); }  // block_loss_functions.rs:15-17
-
-__device__ __forceinline__ float req_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = __fadd_rn(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
-// ((a.x b.x + a.y b.y) + a.z b.z) + a.w b.w, every operation rounded (the build has no contraction)
-__device__ __forceinline__ float req_dot4(const float4 &a, const float4 &b) {
-    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fmul_rn(a.z, b.z)), __fmul_rn(a.w, b.w));
-}
-
-// kernels.hip packed_weight / packed_weights4, restated: the bucket's f16 pattern to f32 exactly, then ONE multiply and ONE add, unfused
-__device__ __forceinline__ float req_packed_weight(uint32_t bucket16, float increment, float mn) {
-    const _Float16 h = __builtin_bit_cast(_Float16, (unsigned short)bucket16);
-    return __fadd_rn(mn, __fmul_rn((float)h, increment));
-}
-__device__ __forceinline__ float4 req_packed_weights4(uint2 raw, float increment, float mn) {
-    return make_float4(req_packed_weight(raw.x & 0xffffu, increment, mn), req_packed_weight(raw.x >> 16, increment, mn),
-                       req_packed_weight(raw.y & 0xffffu, increment, mn), req_packed_weight(raw.y >> 16, increment, mn));
-}
 
 __global__ __launch_bounds__(kReqBaseThreads) void requests_base_kernel(const RequestsParams p) {
     __shared__ float s_part[kReqBaseThreads / 64];
@@ -88,7 +65,7 @@ __global__ __launch_bounds__(kReqBaseThreads) void requests_base_kernel(const Re
             s = __fadd_rn(s, __fmul_rn(0.5f, __fmul_rn(t, t)));
     }
     for (uint32_t f = tid; f < F; f += kReqBaseThreads) s = __fadd_rn(s, __fmul_rn(-0.5f, dcf[f]));
-    s = req_wave_sum(s);
+    s = wave_sum(s);
     if ((tid & 63) == 0) s_part[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) {
@@ -118,20 +95,15 @@ __global__ __launch_bounds__(64 * kReqMaxWaves) void requests_predict_kernel(con
     const uint32_t stop = p.ffm_off[ex + 1];
     while (pos < stop) {
         const uint32_t f = p.ffm_fld[pos];
-        uint32_t end = pos + 1;  // the field's run of entries [pos, end): 64 field bytes per look
-        while (end < stop) {
-            const uint32_t i = end + lane;
-            const unsigned long long same = __ballot(i < stop && p.ffm_fld[i] == f);
-            const uint32_t cnt = ~same ? (uint32_t)__builtin_ctzll(~same) : 64u;
-            end += cnt;
-            if (cnt < 64u) break;
-        }
+        const uint32_t end = field_run_end(p.ffm_fld, pos, stop, lane);  // the field's run of entries [pos, end)
         const float *Trow = T + (size_t)f * R;
         for (uint32_t c = 0; c < chunks; ++c) {
             const uint32_t e0 = (c * 64u + lane) * 4u;
             const bool inb = e0 < R;
             const uint32_t z = inb ? e0 / k : 0u;
             const bool self = inb && z == f;
+            // (this loop and the gathered-fields mask below stand in requests_head_kernel too, word for word: as forced-inline helpers, in every shape
+            // tried, they changed this kernel's ISA)
             float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             float fd = 0.0f;  // sum_i v_i^2 |w_i[f]|^2, this lane's four floats of the own slot
             for (uint32_t i = pos; i < end; i += ROWS) {
@@ -150,7 +122,7 @@ __global__ __launch_bounds__(64 * kReqMaxWaves) void requests_predict_kernel(con
                 }
                 if (PK) {
 #pragma unroll
-                    for (int u = 0; u < ROWS; ++u) r[u] = req_packed_weights4(raw[PK ? u : 0], p.q_increment, p.q_min);
+                    for (int u = 0; u < ROWS; ++u) r[u] = packed_weights4(raw[PK ? u : 0], p.q_increment, p.q_min);
                 }
 #pragma unroll
                 for (int u = 0; u < ROWS; ++u) {
@@ -160,30 +132,27 @@ __global__ __launch_bounds__(64 * kReqMaxWaves) void requests_predict_kernel(con
                         acc.y = __fadd_rn(acc.y, t.y);
                         acc.z = __fadd_rn(acc.z, t.z);
                         acc.w = __fadd_rn(acc.w, t.w);
-                        if (self) fd = __fadd_rn(fd, req_dot4(t, t));
+                        if (self) fd = __fadd_rn(fd, dot4(t, t));
                     }
                 }
             }
             if (inb) {
-                part = __fadd_rn(part, req_dot4(acc, *reinterpret_cast<const float4 *>(Trow + e0)));  // <D[f], d_T[f R ..)>, z == f included
+                part = __fadd_rn(part, dot4(acc, *reinterpret_cast<const float4 *>(Trow + e0)));  // <D[f], d_T[f R ..)>, z == f included
                 if (self) {
-                    part = __fadd_rn(part, __fmul_rn(0.5f, __fsub_rn(req_dot4(acc, acc), fd)));  // (one feature: exactly 0)
+                    part = __fadd_rn(part, __fmul_rn(0.5f, __fsub_rn(dot4(acc, acc), fd)));  // (one feature: exactly 0)
                 } else {
                     const uint32_t w = z >> 6;
                     const unsigned long long word = w == 0 ? g0 : w == 1 ? g1 : w == 2 ? g2 : g3;
                     if ((word >> (z & 63u)) & 1ull) {  // an earlier gathered field: <D[f][z], D[z][f]> with D[z] from its slice
                         const uint32_t slot = (w > 0 ? __popcll(g0) : 0) + (w > 1 ? __popcll(g1) : 0) + (w > 2 ? __popcll(g2) : 0) +
                                               __popcll(word & ((1ull << (z & 63u)) - 1ull));
-                        part = __fadd_rn(part, req_dot4(acc, *reinterpret_cast<const float4 *>(park + (size_t)slot * R + f * k + (e0 - z * k))));
+                        part = __fadd_rn(part, dot4(acc, *reinterpret_cast<const float4 *>(park + (size_t)slot * R + f * k + (e0 - z * k))));
                     }
                 }
                 if (ns < p.slots) *reinterpret_cast<float4 *>(park + (size_t)ns * R + e0) = acc;  // (always: a candidate fills at most min(F, its entries) slices)
             }
         }
-        // the slice is read by OTHER lanes of this wave when a later field completes: order the LDS accesses, wave-wide (no workgroup barrier)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();  // the slice is read by OTHER lanes of this wave when a later field completes
         const unsigned long long bit = 1ull << (f & 63u);
         const uint32_t fw = f >> 6;
         g0 |= fw == 0 ? bit : 0ull;
@@ -197,19 +166,8 @@ __global__ __launch_bounds__(64 * kReqMaxWaves) void requests_predict_kernel(con
         const uint32_t le = p.lr_off[ex + 1];
         for (uint32_t i = p.lr_off[ex] + lane; i < le; i += 64u) part = __fadd_rn(part, __fmul_rn(p.lr[2ull * p.lr_hash[i]], p.lr_val[i]));
     }
-    const float wsum = __fadd_rn(req_wave_sum(part), p.base[ci]);
-    if (lane == 0) {
-        float pr;  // block_loss_functions.rs:105-153: clip +-50, NaN -> 0.5
-        if (isnan(wsum))
-            pr = req_logistic(0.0f);
-        else if (wsum < -50.0f)
-            pr = req_logistic(-50.0f);
-        else if (wsum > 50.0f)
-            pr = req_logistic(50.0f);
-        else
-            pr = req_logistic(wsum);
-        p.pred[ex] = pr;
-    }
+    const float wsum = __fadd_rn(wave_sum(part), p.base[ci]);
+    if (lane == 0) p.pred[ex] = clipped_prediction(wsum);
 }
 
 bool requests_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out) {
@@ -246,7 +204,8 @@ hipError_t launch_requests(const RequestsParams &p, const RequestsShape &shape, 
     return hipErrorInvalidValue;
 }
 
-// fwgpu_setup_cache on a packed regressor with caches enabled: the header comment of this file states the sums' order
+// fwgpu_setup_cache on a packed regressor with caches enabled: the header comment of this file states the sums' order.  Its loop is NOT the predict
+// kernel's: the self term is (ss v) v from w, the order an f32 regressor's cache holds, where the predict kernel adds dot4(t, t) of t = w v.
 __global__ __launch_bounds__(64) void packed_cache_build_kernel(const PackedCacheBuild p) {
     const uint32_t f = blockIdx.x, lane = threadIdx.x;
     const uint32_t k = p.k, R = p.R;
@@ -278,7 +237,7 @@ __global__ __launch_bounds__(64) void packed_cache_build_kernel(const PackedCach
 #pragma unroll
             for (int u = 0; u < kReqRows; ++u) {
                 if (i + u < lo + n) {
-                    const float4 w = req_packed_weights4(raw[u], p.q_increment, p.q_min);
+                    const float4 w = packed_weights4(raw[u], p.q_increment, p.q_min);
                     acc.x = __fadd_rn(acc.x, __fmul_rn(w.x, v[u]));
                     acc.y = __fadd_rn(acc.y, __fmul_rn(w.y, v[u]));
                     acc.z = __fadd_rn(acc.z, __fmul_rn(w.z, v[u]));
@@ -292,7 +251,7 @@ __global__ __launch_bounds__(64) void packed_cache_build_kernel(const PackedCach
         }
         *reinterpret_cast<float4 *>(p.T + (size_t)z * R + f * k + (e0 - z * k)) = acc;
     }
-    dc = req_wave_sum(dc);  // (every lane of the wave is here: the loop above has no early exit)
+    dc = wave_sum(dc);  // (every lane of the wave is here: the loop above has no early exit)
     if (lane == 0) {
         p.dcf[f] = dc;
         p.cnt[f] = n;

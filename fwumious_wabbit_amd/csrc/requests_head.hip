@@ -30,7 +30,7 @@
 
 #include <algorithm>
 
-#include "fwgpu_internal.h"
+#include "fwgpu_device.h"
 
 namespace fwgpu {
 
@@ -38,18 +38,6 @@ static constexpr uint32_t kRhBaseThreads = 256;
 static constexpr uint32_t kRhMaxWaves = 4;         // waves (= candidates) per workgroup
 static constexpr size_t kRhLdsTarget = 64 * 1024;  // ... as many as keep the workgroup at or below this
 static constexpr int kRhRows = 4;                  // rows of a field in flight per lane
-
-// ((a.x b.x + a.y b.y) + a.z b.z) + a.w b.w, every operation rounded (the build has no contraction)
-__device__ __forceinline__ float rh_dot4(const float4 &a, const float4 &b) {
-    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fmul_rn(a.z, b.z)), __fmul_rn(a.w, b.w));
-}
-
-// LDS accesses of OTHER lanes of this wave ordered against this lane's, wave-wide (no workgroup barrier)
-__device__ __forceinline__ void rh_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(kRhBaseThreads) void requests_head_base_kernel(const RequestsHeadParams p) {
     const uint32_t c = blockIdx.x;
@@ -59,10 +47,8 @@ __global__ __launch_bounds__(kRhBaseThreads) void requests_head_base_kernel(cons
     const uint32_t *cnt = reinterpret_cast<const uint32_t *>(dcf + F);  // (one allocation: T, dcf, cnt -- fwgpu_setup_cache)
     float *row = p.q.base + (size_t)c * p.NT;
     for (uint32_t t = threadIdx.x; t < p.NT; t += kRhBaseThreads) {
-        uint32_t i = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-        while ((i + 1) * (i + 2) / 2 <= t) ++i;
-        while (i * (i + 1) / 2 > t) --i;
-        const uint32_t j = t - i * (i + 1) / 2;
+        const uint2 ij = tri_slot(t);
+        const uint32_t i = ij.x, j = ij.y;
         const float *a = T + (size_t)i * R + j * k, *b = T + (size_t)j * R + i * k;
         float d = 0.0f;
         for (uint32_t kk = 0; kk < k; ++kk) d = __fadd_rn(d, __fmul_rn(a[kk], b[kk]));
@@ -86,30 +72,24 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
     const uint32_t *cnt = reinterpret_cast<const uint32_t *>(dcf + F);
     const uint32_t chunks = (R + 255u) >> 8;
     for (uint32_t t = lane; t < NT; t += 64u) row[t] = p.q.base[(size_t)ci * NT + t];
-    rh_wave_sync();
+    wave_lds_sync();
     unsigned long long g0 = 0, g1 = 0, g2 = 0, g3 = 0;  // bit f: field f has been gathered and parked (wave-uniform)
     uint32_t ns = 0;                                     // ... how many: the next free slice
     uint32_t pos = p.q.ffm_off[ex];
     const uint32_t stop = p.q.ffm_off[ex + 1];
     while (pos < stop) {
         const uint32_t f = p.q.ffm_fld[pos];
-        uint32_t end = pos + 1;  // the field's run of entries [pos, end): 64 field bytes per look
-        while (end < stop) {
-            const uint32_t i = end + lane;
-            const unsigned long long same = __ballot(i < stop && p.q.ffm_fld[i] == f);
-            const uint32_t n_same = ~same ? (uint32_t)__builtin_ctzll(~same) : 64u;
-            end += n_same;
-            if (n_same < 64u) break;
-        }
+        const uint32_t end = field_run_end(p.q.ffm_fld, pos, stop, lane);  // the field's run of entries [pos, end)
         const float *Trow = T + (size_t)f * R;
         const uint32_t td = f * (f + 1) / 2 + f;
         if (lane == 0) row[td] = -dcf[f];  // the diagonal anew: the chunks add |S + D|^2 - fd part by part
-        rh_wave_sync();
+        wave_lds_sync();
         for (uint32_t c = 0; c < chunks; ++c) {
             const uint32_t e0 = (c * 64u + lane) * 4u;
             const bool inb = e0 < R;
             const uint32_t z = inb ? e0 / k : 0u;
             const bool self = inb && z == f;
+            // (the gather loop and the gathered-fields mask of requests_predict_kernel<false, ROWS>, word for word: see there)
             float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             float fd = 0.0f;  // sum_i v_i^2 |w_i[f]|^2, this lane's four floats of the own slot
             for (uint32_t i = pos; i < end; i += ROWS) {
@@ -130,7 +110,7 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
                         acc.y = __fadd_rn(acc.y, t.y);
                         acc.z = __fadd_rn(acc.z, t.z);
                         acc.w = __fadd_rn(acc.w, t.w);
-                        if (self) fd = __fadd_rn(fd, rh_dot4(t, t));
+                        if (self) fd = __fadd_rn(fd, dot4(t, t));
                     }
                 }
             }
@@ -139,15 +119,15 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
                 const float4 s = *reinterpret_cast<const float4 *>(Trow + e0);  // S[z][f]
                 if (self) {
                     const float4 u = make_float4(__fadd_rn(s.x, acc.x), __fadd_rn(s.y, acc.y), __fadd_rn(s.z, acc.z), __fadd_rn(s.w, acc.w));
-                    val = __fsub_rn(rh_dot4(u, u), fd);
+                    val = __fsub_rn(dot4(u, u), fd);
                 } else {
-                    val = rh_dot4(acc, s);  // <D[f][z], S[z][f]>
+                    val = dot4(acc, s);  // <D[f][z], S[z][f]>
                     const uint32_t w = z >> 6;
                     const unsigned long long word = w == 0 ? g0 : w == 1 ? g1 : w == 2 ? g2 : g3;
                     if ((word >> (z & 63u)) & 1ull) {  // an earlier gathered field: <D[f][z], D[z][f]> with D[z] from its slice
                         const uint32_t slot = (w > 0 ? __popcll(g0) : 0) + (w > 1 ? __popcll(g1) : 0) + (w > 2 ? __popcll(g2) : 0) +
                                               __popcll(word & ((1ull << (z & 63u)) - 1ull));
-                        val = __fadd_rn(val, rh_dot4(acc, *reinterpret_cast<const float4 *>(park + (size_t)slot * R + f * k + (e0 - z * k))));
+                        val = __fadd_rn(val, dot4(acc, *reinterpret_cast<const float4 *>(park + (size_t)slot * R + f * k + (e0 - z * k))));
                     }
                 }
                 if (ns < p.q.slots) *reinterpret_cast<float4 *>(park + (size_t)ns * R + e0) = acc;  // (always: a candidate fills at most min(F, its entries) slices)
@@ -164,14 +144,14 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
                 float *dst = row + hi * (hi + 1) / 2 + lo;
                 *dst = __fadd_rn(*dst, sum);
             }
-            rh_wave_sync();  // (a slot across the chunk edge: the next chunk's lane 0 adds to what this chunk's leader left)
+            wave_lds_sync();  // (a slot across the chunk edge: the next chunk's lane 0 adds to what this chunk's leader left)
         }
         if (lane == 0) {
             const float d = row[td];
             row[td] = cnt[f] + (end - pos) <= 1u ? 0.0f : __fmul_rn(0.5f, d);
         }
         // the slice and the row are read by OTHER lanes of this wave when a later field completes
-        rh_wave_sync();
+        wave_lds_sync();
         const unsigned long long bit = 1ull << (f & 63u);
         const uint32_t fw = f >> 6;
         g0 |= fw == 0 ? bit : 0ull;
@@ -183,8 +163,8 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
     }
     float *x = p.xbuf + (size_t)ex * p.X;
     for (uint32_t t = lane; t < NT; t += 64u) x[p.C + t] = row[t];
-    // combo slots: lane l owns combo cb + l; the products of 64 entries at a time are formed once and handed round in buffer order
     const uint32_t l0 = p.q.lr_off[ex], l1 = p.q.has_lr ? p.q.lr_off[ex + 1] : l0;
+    // (head_combo_slots, open-coded: inlined here the helper changes this kernel's ISA)
     for (uint32_t cb = 0; cb < p.C; cb += 64u) {
         float acc = 0.0f;
         for (uint32_t b0 = l0; b0 < l1; b0 += 64u) {
@@ -199,10 +179,7 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
         }
         if (cb + lane < p.C) x[cb + lane] = acc;
     }
-    if (lane == 0) {
-        p.yi[2 * (size_t)ex] = p.label[ex];
-        p.yi[2 * (size_t)ex + 1] = p.importance[ex];
-    }
+    if (lane == 0) store_label_importance(p.yi, p.label, p.importance, ex);
 }
 
 // the launch-shape rule of requests_launch_shape with the candidate's triangle row beside its slices
