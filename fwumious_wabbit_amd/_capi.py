@@ -30,6 +30,7 @@ ROUTE_PACKED_HEAD = 7
 KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED, KERNEL_REQUESTS, KERNEL_PACKED_REQUESTS, KERNEL_HEAD_REQUESTS = 0, 1, 2, 3, 4, 5, 6
 KERNEL_HEAD_FUSED = 7
 KERNEL_PACKED_HEAD = 8
+KERNEL_PACKED_HEAD_REQUESTS = 9
 LAUNCH_INFO = ("family", "chunks", "window", "chain", "no_kept_rows", "lds_keep", "threads", "lds_bytes")
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
@@ -263,6 +264,8 @@ def lib():
         "fwgpu_packed_caches_state": [vp, P(i32), P(u64)],
         "fwgpu_enable_head_requests": [vp],
         "fwgpu_head_requests_state": [vp, P(i32)],
+        "fwgpu_packed_enable_head_requests": [vp],
+        "fwgpu_packed_head_requests_state": [vp, P(i32)],
         "fwgpu_enable_fused_head": [vp],
         "fwgpu_fused_head_state": [vp, P(i32), P(u64), P(u64)],
         "fwgpu_debug_head_forward_time": [vp, u32, i32, u32, P(C.c_float), vp],

@@ -46,7 +46,7 @@ int fwgpu_setup_cache(fwgpu_regressor *r, const fwgpu_lr_entry *lr, uint32_t n_l
                       uint32_t n_ffm, fwgpu_block_cache **cache) {
     if (!r || !cache) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if ((n_lr && !lr) || (n_ffm && !ffm)) return fail(FWGPU_ERR_INVALID, "NULL entry buffer");
-    if (!r->packed_caches)
+    if (!r->keeps_packed_caches())
         if (int rcp = refuse_packed(r, "setup_cache (a device-side context cache)")) return rcp;
     FWGPU_HIP(hipSetDevice(r->device));
     const uint32_t F = r->cfg.ffm_k ? r->cfg.ffm_num_fields : 0, R = F * r->cfg.ffm_k;
@@ -260,7 +260,8 @@ extern "C" {
 int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *c) {
     if (!b) return fail(FWGPU_ERR_INVALID, "NULL batch");
     if (c && c->owner != b->owner) return fail(FWGPU_ERR_INVALID, "cache belongs to another regressor");
-    if (c && b->owner && b->owner->packed()) {  // (fwgpu_packed_enable_caches: a packed regressor has no other cache) the set of ONE on the requests route
+    // (fwgpu_packed_enable_caches, fwgpu_packed_enable_head_requests: a packed regressor has no other cache) the set of ONE on the requests route
+    if (c && b->owner && b->owner->packed()) {
         if (b->records)
             return fail(FWGPU_ERR_INVALID, "set_cache: a packed regressor serves a cache through the entry route only: a record batch with a cache is not served "
                                            "(send an entry batch of the buffers fwgpu_block_cache_filter leaves)");
@@ -382,6 +383,29 @@ int fwgpu_enable_head_requests(fwgpu_regressor *r) {
 int fwgpu_head_requests_state(const fwgpu_regressor *r, int *enabled) {
     if (!r || !enabled) return fail(FWGPU_ERR_INVALID, "NULL argument");
     *enabled = r->head_requests ? 1 : 0;
+    return FWGPU_OK;
+}
+
+// The two switches above refuse a packed regressor with a deep head, and keep doing so; this one is that regressor's own.  After it fwgpu_setup_cache
+// builds caches from the buckets (packed_cache_build_kernel, held to the weights epoch) and a batch with a set takes the requests route
+// (requests_head.hip on the packed table); a batch without one keeps FWGPU_ROUTE_PACKED_HEAD.
+int fwgpu_packed_enable_head_requests(fwgpu_regressor *r) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    const char *why = nullptr;
+    if (!r->packed()) why = r->nn.n_layers ? "the regressor's FFM weights are f32 (fwgpu_enable_head_requests is the switch of an f32 regressor with a deep head)"
+                                           : "the regressor's FFM weights are f32 and it has no deep head: the requests route serves it without a switch";
+    else if (!r->nn.n_layers) why = "the packed regressor has no deep head (fwgpu_packed_enable_caches is the switch of a headless packed regressor)";
+    else if (r->cfg.ffm_k == 0) why = "the model has no FFM block";
+    else if (r->cfg.ffm_k % 4 != 0) why = "ffm_k is no multiple of 4 (the requests kernel has no one-float-per-lane form)";
+    else if (r->cfg.ffm_num_fields > 256) why = "more than 256 fields";
+    if (why) return fail(FWGPU_ERR_INVALID, std::string("packed_enable_head_requests: ") + why);
+    r->packed_head_requests = true;
+    return FWGPU_OK;
+}
+
+int fwgpu_packed_head_requests_state(const fwgpu_regressor *r, int *enabled) {
+    if (!r || !enabled) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *enabled = r->packed_head_requests ? 1 : 0;
     return FWGPU_OK;
 }
 

@@ -487,7 +487,7 @@ bool requests_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_
 hipError_t launch_requests(const RequestsParams &p, const RequestsShape &shape, hipStream_t stream, int rows = 0);
 // ... on a model with a deep head (requests_head.hip; fwgpu_enable_head_requests): the same batch and set, the head's input x in place of the logit
 struct RequestsHeadParams {
-    RequestsParams q;               // (q.base: [n_caches * NT] every cache's triangle row from S alone; q.pred, q.ffm_q are not read)
+    RequestsParams q;               // (q.base: [n_caches * NT] every cache's triangle row from S alone; q.pred is not read; q.ffm_q: the packed table)
     const uint16_t *lr_combo;       // combo slot of each LR entry
     const float *label;             // [n] and importance [n]
     const float *importance;
@@ -497,7 +497,8 @@ struct RequestsHeadParams {
 };
 // false: one wave's slices and triangle row do not fit lds_limit bytes
 bool requests_head_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t lds_limit, RequestsShape *out);
-hipError_t launch_requests_head(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream);
+// rows: as launch_requests (p.q.ffm_q != NULL: the packed table, fwgpu_packed_enable_head_requests)
+hipError_t launch_requests_head(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream, int rows = 0);
 // ---- the head's inputs of a whole predict-only batch on a packed table (head_packed.hip; launch.cpp run_batch_packed_head)
 struct PackedHeadParams {
     const uint16_t *ffm_q;          // the table of f16 bucket numbers ...
@@ -639,6 +640,11 @@ struct fwgpu_regressor {
     bool packed_caches = false;
     uint64_t weights_epoch = 0;
     bool head_requests = false;  // fwgpu_enable_head_requests: the one-way switch that lets a deep-head model take the requests route (requests_head.hip)
+    // fwgpu_packed_enable_head_requests: the one-way switch of a PACKED regressor with a deep head -- it keeps context caches built from the buckets (as
+    // packed_caches, under weights_epoch) and its batches with a set take the requests route (requests_head.hip, PK = true)
+    bool packed_head_requests = false;
+    bool keeps_packed_caches() const { return packed_caches || packed_head_requests; }
+    bool serves_head_requests() const { return head_requests || packed_head_requests; }
     bool fused_head = false;     // fwgpu_enable_fused_head: the one-way switch that sends small predict-only slabs through head_forward_fused_kernel (head_fused.hip)
     int placement_tries = 0;                     // candidate allocations timed for d_ffm_acc (regressor.cpp: place_ffm_acc)
     float placement_ms_lo = 0, placement_ms_hi = 0;  // fastest / slowest pair probe among them

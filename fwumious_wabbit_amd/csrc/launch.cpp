@@ -321,8 +321,8 @@ static int run_batch_packed(fwgpu_regressor *r, fwgpu_batch *b, int mode, int up
 // Why the requests kernels (requests.hip) do not serve this regressor / batch shape, or NULL.  Asked when a set is attached and again at every launch.
 const char *requests_refusal(const fwgpu_regressor *r, const fwgpu_batch *b) {
     const uint32_t k = r->cfg.ffm_k, F = r->cfg.ffm_num_fields;
-    if (r->packed() && !r->packed_caches) return "a packed regressor keeps no device-side context cache";
-    if (r->nn.n_layers && !r->head_requests) return "models with a deep head are not served by the requests route (fwgpu_batch_set_cache serves them)";
+    if (r->packed() && !r->keeps_packed_caches()) return "a packed regressor keeps no device-side context cache";
+    if (r->nn.n_layers && !r->serves_head_requests()) return "models with a deep head are not served by the requests route (fwgpu_batch_set_cache serves them)";
     if (b->records) return "a record batch is not served by the requests route (an entry batch of the filtered buffers is)";
     if (b->host_copy) return "the batch holds an oversize example (more than 4096 entries of a kind, or beyond the fused kernel's LDS)";
     if (k == 0) return "the model has no FFM block";
@@ -334,14 +334,14 @@ const char *requests_refusal(const fwgpu_regressor *r, const fwgpu_batch *b) {
 
 // predict-only launch of an entry batch with a cache per example: base(S) of every cache of the set, then one wavefront per candidate, on `stream`
 // (`rows`: the packed predict kernel's rows in flight, 0 = its default -- fwgpu_debug_requests_time)
-static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const RequestsParams &q, hipStream_t stream);
+static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const RequestsParams &q, hipStream_t stream, int rows);
 static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hipStream_t stream, int rows = 0) {
     if (update) return fail(FWGPU_ERR_INVALID, "a batch with a cache per example (fwgpu_batch_set_caches) is predict-only: update must be 0");
     if (const char *why = requests_refusal(r, b)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + why);
     for (const fwgpu_block_cache *c : b->req_caches)
         if (cache_is_stale(r, c)) return fail(FWGPU_ERR_INVALID, std::string("requests route: ") + kStaleCache);
     const uint32_t F = r->cfg.ffm_num_fields, k = r->cfg.ffm_k, R = F * k;
-    const bool head = r->nn.n_layers != 0;  // (fwgpu_enable_head_requests: requests_refusal let it through)
+    const bool head = r->nn.n_layers != 0;  // (fwgpu_enable_head_requests, fwgpu_packed_enable_head_requests: requests_refusal let it through)
     RequestsShape shape;
     if (!head && !requests_launch_shape(F, R, b->max_ffm, r->lds_per_cu, &shape))
         return fail(FWGPU_ERR_RANGE, "requests route: min(fields, the batch's largest FFM entry count) * F * k floats of one candidate do not fit the 160 KiB LDS");
@@ -369,7 +369,7 @@ static int run_batch_requests(fwgpu_regressor *r, fwgpu_batch *b, int update, hi
     p.R = R;
     p.slots = shape.slots;
     p.has_lr = r->cfg.wiring == FWGPU_WIRING_REGRESSOR;
-    if (head) return run_batch_head_requests(r, b, p, stream);
+    if (head) return run_batch_head_requests(r, b, p, stream, rows);
     launched_shape(r, r->packed() ? FWGPU_KERNEL_PACKED_REQUESTS : FWGPU_KERNEL_REQUESTS, shape.chunks, shape.threads, shape.lds_bytes);
     FWGPU_HIP(launch_requests(p, shape, stream, rows));
     return FWGPU_OK;
@@ -449,7 +449,8 @@ static int run_batch_head_predict(fwgpu_regressor *r, fwgpu_batch *b, hipStream_
 
 // ... with a cache per example (fwgpu_enable_head_requests): every cache's triangle row, one wavefront per candidate forms its x from the cache and its
 // own few features (requests_head.hip), then the same layers.  Any batch size: the frozen weights order nothing, and there is no other route to fall to.
-static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const RequestsParams &q, hipStream_t stream) {
+// A packed regressor (fwgpu_packed_enable_head_requests) runs the same launches, the candidate's rows gathered from the buckets (q.ffm_q).
+static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const RequestsParams &q, hipStream_t stream, int rows) {
     RequestsShape shape;
     if (!requests_head_launch_shape(q.F, q.R, b->max_ffm, r->lds_per_cu, &shape))
         return fail(FWGPU_ERR_RANGE, "requests route: min(fields, the batch's largest FFM entry count) * F * k + F (F + 1) / 2 floats of one candidate do not fit the 160 KiB LDS");
@@ -466,8 +467,8 @@ static int run_batch_head_requests(fwgpu_regressor *r, fwgpu_batch *b, const Req
     p.C = r->cfg.num_combos;
     p.NT = q.F * (q.F + 1) / 2;
     p.X = r->nn.X;
-    launched_shape(r, FWGPU_KERNEL_HEAD_REQUESTS, shape.chunks, shape.threads, shape.lds_bytes);
-    FWGPU_HIP(launch_requests_head(p, shape, stream));
+    launched_shape(r, r->packed() ? FWGPU_KERNEL_PACKED_HEAD_REQUESTS : FWGPU_KERNEL_HEAD_REQUESTS, shape.chunks, shape.threads, shape.lds_bytes);
+    FWGPU_HIP(launch_requests_head(p, shape, stream, rows));
     return head_predict_slabs(r, b, stream);
 }
 
@@ -536,8 +537,9 @@ static int run_batch_fused(fwgpu_regressor *r, fwgpu_batch *b, int mode, int upd
 // The FWGPU_ROUTE_* a batch takes, from the regressor and the batch alone -- also where that route then refuses the launch (an updating launch of a
 // packed regressor or of a batch with a set) and, for a packed regressor, where there is nothing to launch.
 static int32_t pick_route(const fwgpu_regressor *r, const fwgpu_batch *b, int mode, int update) {
-    if (r->packed()) {  // fwgpu_packed_enable_caches: one cache (fwgpu_batch_set_cache) or a set
-        if (r->nn.n_layers) return FWGPU_ROUTE_PACKED_HEAD;  // (no caches on such a regressor; every n, both modes)
+    if (r->packed()) {  // fwgpu_packed_enable_caches, fwgpu_packed_enable_head_requests: one cache (fwgpu_batch_set_cache) or a set
+        // (a deep head: without the switch no caches on such a regressor; without a set the whole example, every n, both modes)
+        if (r->nn.n_layers) return r->packed_head_requests && b->n && !b->req_caches.empty() ? FWGPU_ROUTE_REQUESTS : FWGPU_ROUTE_PACKED_HEAD;
         return r->packed_caches && b->n && !b->req_caches.empty() ? FWGPU_ROUTE_REQUESTS : FWGPU_ROUTE_PACKED;
     }
     if (b->n == 0) return FWGPU_ROUTE_NONE;

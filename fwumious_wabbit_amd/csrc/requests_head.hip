@@ -1,4 +1,4 @@
-// Candidates of MANY requests in one predict-only launch on a model with a DEEP HEAD (fwgpu_enable_head_requests; DESIGN.md 4.8 "Deep heads").
+// Candidates of MANY requests in one predict-only launch on a model with a DEEP HEAD (fwgpu_enable_head_requests, on packed weights fwgpu_packed_enable_head_requests; DESIGN.md 4.8 "Deep heads").
 //
 // requests.hip gives a candidate the SUM of its pair terms; the head wants them one by one: x = [C per-combo LR sums | NT = F (F + 1) / 2 triangle
 // slots], slot t = i (i + 1) / 2 + j, j <= i -- the x of kernels.hip's emit_x branch.  With S the cached field sums (d_T[f R .. f R + R) is
@@ -25,7 +25,17 @@
 //                          round in buffer order) and writes {label, importance} for head_step.  No atomics anywhere: two launches, both modes,
 //                          grouped or interleaved candidates give the same bits of x.
 // LDS per wave: min(F, the batch's largest FFM entry count) * R + NT floats; all waves' slices first (16-byte aligned), their rows behind them.
-// The layers then take x through head.hip's MFMA GEMMs (launch.cpp run_batch_head_requests).  f32 tables only.
+// The layers then take x through head.hip's MFMA GEMMs or head_fused.hip (launch.cpp run_batch_head_requests).
+//
+// PACKED TABLES (fwgpu_packed_enable_head_requests on a regressor of fwgpu_model_load_packed_head).  requests_head_kernel is a template over the table's
+// storage, as requests_predict_kernel is: PK = true reads a lane's four weights of a row as ONE 8-byte load of four f16 bucket numbers from
+// p.q.ffm_q + h + e0 (rows start on a multiple of 4 buckets), issues the loads of all ROWS rows in flight first and then converts them by
+// packed_weights4 (fwgpu_device.h): f16 -> f32 exactly, one multiply, one add, unfused.  Every statement behind the conversion is the f32 statement in
+// the f32 order, so x has the bits the f32 kernel forms on a table that holds the dequantised values.  The cached sums stay f32: T, dcf and cnt come
+// from packed_cache_build_kernel (requests.hip) in the layout requests_head_base_kernel reads, and that kernel serves both storages as it is.
+// A row that crosses the chunk edge inside a slot (30 x 12) never reaches the packed form: such a shape is refused when the packed table is loaded;
+// the chunk-order add above is there for f32 tables.  Rows in flight on a packed table: 4, the depth the headless packed kernel kept over 8
+// (fwgpu_debug_requests_time takes 4 or 8 for the A/B; scripts/bench_serving_packed_head_requests.py records both).
 #include <math.h>
 
 #include <algorithm>
@@ -38,6 +48,7 @@ static constexpr uint32_t kRhBaseThreads = 256;
 static constexpr uint32_t kRhMaxWaves = 4;         // waves (= candidates) per workgroup
 static constexpr size_t kRhLdsTarget = 64 * 1024;  // ... as many as keep the workgroup at or below this
 static constexpr int kRhRows = 4;                  // rows of a field in flight per lane
+static constexpr int kRhRowsPacked = 4;            // ... on a packed table (half the bytes per row; the depth the headless packed kernel kept over 8)
 
 __global__ __launch_bounds__(kRhBaseThreads) void requests_head_base_kernel(const RequestsHeadParams p) {
     const uint32_t c = blockIdx.x;
@@ -57,7 +68,8 @@ __global__ __launch_bounds__(kRhBaseThreads) void requests_head_base_kernel(cons
     }
 }
 
-template <int ROWS>
+// PK: the table holds f16 bucket numbers (p.q.ffm_q); ROWS: rows of a field in flight per lane
+template <bool PK, int ROWS>
 __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const RequestsHeadParams p) {
     extern __shared__ __align__(16) float rh_lds[];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
@@ -89,18 +101,26 @@ __global__ __launch_bounds__(64 * kRhMaxWaves) void requests_head_kernel(const R
             const bool inb = e0 < R;
             const uint32_t z = inb ? e0 / k : 0u;
             const bool self = inb && z == f;
-            // (the gather loop and the gathered-fields mask of requests_predict_kernel<false, ROWS>, word for word: see there)
+            // (the gather loop and the gathered-fields mask of requests_predict_kernel<PK, ROWS>, word for word: see there)
             float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             float fd = 0.0f;  // sum_i v_i^2 |w_i[f]|^2, this lane's four floats of the own slot
             for (uint32_t i = pos; i < end; i += ROWS) {
                 float4 r[ROWS];
+                uint2 raw[PK ? ROWS : 1];  // packed rows: the buckets as loaded; converted once all loads are issued
                 float v[ROWS];
 #pragma unroll
                 for (int u = 0; u < ROWS; ++u) {  // all loads first (an entry beyond the run reads the run's first row again and is not added)
                     const uint32_t ii = i + u < end ? i + u : pos;
                     v[u] = p.q.ffm_val[ii];
                     const uint32_t h = p.q.ffm_hash[ii];
-                    r[u] = inb ? *reinterpret_cast<const float4 *>(p.q.ffm_w + h + e0) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (PK)
+                        raw[PK ? u : 0] = inb ? *reinterpret_cast<const uint2 *>(p.q.ffm_q + h + e0) : make_uint2(0u, 0u);
+                    else
+                        r[u] = inb ? *reinterpret_cast<const float4 *>(p.q.ffm_w + h + e0) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                }
+                if (PK) {
+#pragma unroll
+                    for (int u = 0; u < ROWS; ++u) r[u] = packed_weights4(raw[PK ? u : 0], p.q.q_increment, p.q.q_min);
                 }
 #pragma unroll
                 for (int u = 0; u < ROWS; ++u) {
@@ -195,15 +215,26 @@ bool requests_head_launch_shape(uint32_t F, uint32_t R, uint32_t max_ffm, size_t
     return true;
 }
 
-hipError_t launch_requests_head(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(requests_head_kernel<kRhRows>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds_bytes);
+template <bool PK, int ROWS>
+static hipError_t launch_requests_head_as(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(requests_head_kernel<PK, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds_bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(requests_head_base_kernel, dim3(p.q.n_caches), dim3(kRhBaseThreads), 0, stream, p);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const uint32_t waves = shape.threads / 64;
-    hipLaunchKernelGGL((requests_head_kernel<kRhRows>), dim3((p.q.n + waves - 1) / waves), dim3(shape.threads), shape.lds_bytes, stream, p);
+    hipLaunchKernelGGL((requests_head_kernel<PK, ROWS>), dim3((p.q.n + waves - 1) / waves), dim3(shape.threads), shape.lds_bytes, stream, p);
     return hipGetLastError();
+}
+
+// p.q.ffm_q != NULL: the packed table.  rows: 0 = the storage's default depth (kRhRows / kRhRowsPacked), 4 or 8 = that depth on the packed table
+// (fwgpu_debug_requests_time: the A/B of the two depths)
+hipError_t launch_requests_head(const RequestsHeadParams &p, const RequestsShape &shape, hipStream_t stream, int rows) {
+    if (!p.q.ffm_q) return launch_requests_head_as<false, kRhRows>(p, shape, stream);
+    if (rows == 0) rows = kRhRowsPacked;
+    if (rows == 4) return launch_requests_head_as<true, 4>(p, shape, stream);
+    if (rows == 8) return launch_requests_head_as<true, 8>(p, shape, stream);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace fwgpu

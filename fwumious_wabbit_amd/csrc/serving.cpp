@@ -15,7 +15,10 @@
 // needs (kernels.hip nn_forward), a request of 256 candidates or more takes the batched head route (launch.cpp run_batch_head_predict), a smaller one
 // the per-example kernel; with --head_requests on the command (fwgpu_enable_head_requests) fwgpu_predictor_predict_requests serves such a model too,
 // through the head-input kernels of requests_head.hip; with --fused_head (fwgpu_enable_fused_head) a batch of any size takes the batched head route and
-// small ones run the whole head in one launch (head_fused.hip).  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
+// small ones run the whole head in one launch (head_fused.hip); with --packed_weights --packed_head_requests (fwgpu_packed_enable_head_requests) a
+// deep-head model on packed weights gets the same: fw_setup_cache builds the cache from the packed table, every cached call takes the ENTRY route
+// through the set of one, and fwgpu_predictor_predict_requests is one launch of requests_head.hip's packed form (fwgpu_predictor_predict_text keeps
+// the host-translated lines).  Predictors created with --packed_weights keep the uncached route (whole line scored), which gives the same result --
 // unless the command also holds --packed_context_cache: the model's regressor then gets fwgpu_packed_enable_caches, fw_setup_cache builds the
 // device cache from the packed table (no record cover: every cached call takes the ENTRY route), and fw_predict_with_cache,
 // fwgpu_predictor_predict_batch(with_cache) and fwgpu_predictor_predict_requests score the filtered candidate against it on the requests kernels.
@@ -246,23 +249,29 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
         if (words[i] == "-i" || words[i] == "--initial_regressor") weights = words[i + 1];
         if (words[i] == "--device") device = std::atoi(words[i + 1].c_str());  // ours: which GPU serves
     }
-    bool packed = false, packed_caches = false, head_requests = false, fused_head = false;
+    bool packed = false, packed_caches = false, head_requests = false, fused_head = false, packed_head_requests = false;
     for (const auto &w : words) {
         if (w.rfind("--initial_regressor=", 0) == 0) weights = w.substr(std::strlen("--initial_regressor="));
         if (w == "--packed_weights") packed = true;  // ours: the FFM weights stay f16 buckets on the device (fwgpu_model_load_packed)
         if (w == "--packed_context_cache") packed_caches = true;  // ours: ... and context caches are built from them (fwgpu_packed_enable_caches)
         if (w == "--head_requests") head_requests = true;  // ours: a deep-head model takes the requests route (fwgpu_enable_head_requests)
         if (w == "--fused_head") fused_head = true;  // ours: small batches run the whole head in one launch (fwgpu_enable_fused_head)
+        // ours: a deep-head model on packed weights keeps context caches and takes the requests route (fwgpu_packed_enable_head_requests)
+        if (w == "--packed_head_requests") packed_head_requests = true;
     }
     if (packed_caches && !packed) {
         set_error("--packed_context_cache is valid only together with --packed_weights (an f32 predictor keeps its context cache without it)");
+        return nullptr;
+    }
+    if (packed_head_requests && !packed) {
+        set_error("--packed_head_requests is valid only together with --packed_weights (on f32 weights --head_requests serves a model with a deep head)");
         return nullptr;
     }
     if (weights.empty()) {
         set_error("Cannot resolve input weights file name");  // the reference panics here (lib.rs:164-167)
         return nullptr;
     }
-    if (head_requests || fused_head) {  // the file's header decides, before a device is touched
+    if (head_requests || fused_head || packed_head_requests) {  // the file's header decides, before a device is touched
         fwgpu_model_instance *mi = nullptr;
         fwgpu_nn_config nn{};
         if (fwgpu_model_read_header(weights.c_str(), nullptr, &mi) != FWGPU_OK) return nullptr;
@@ -279,6 +288,10 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
                              : "--head_requests is valid only on a model with a deep head (fwgpu_predictor_predict_requests serves a headless model without it)");
             return nullptr;
         }
+        if (packed_head_requests && nn.n_layers == 0) {
+            set_error("--packed_head_requests is valid only on a model with a deep head (--packed_context_cache serves a headless model on packed weights)");
+            return nullptr;
+        }
     }
     auto model = std::make_shared<SharedModel>();
     if ((packed ? fwgpu_model_load_packed_head(weights.c_str(), device, &model->vw, &model->mi, &model->re)
@@ -287,6 +300,7 @@ FfiPredictor *new_fw_predictor_prototype(const char *command) {  // lib.rs:150-1
     if (packed_caches && fwgpu_packed_enable_caches(model->re) != FWGPU_OK) return nullptr;
     if (head_requests && fwgpu_enable_head_requests(model->re) != FWGPU_OK) return nullptr;  // (a model without a head: an error, with the reason)
     if (fused_head && fwgpu_enable_fused_head(model->re) != FWGPU_OK) return nullptr;
+    if (packed_head_requests && fwgpu_packed_enable_head_requests(model->re) != FWGPU_OK) return nullptr;
     if (fwgpu_mi_configs(model->mi, device, nullptr, &model->tr, nullptr) != FWGPU_OK) return nullptr;
     auto p = std::make_unique<FfiPredictor>();
     p->model = model;
@@ -326,8 +340,9 @@ float fw_setup_cache(FfiPredictor *ptr, const char *input_buffer) {  // lib.rs:2
     ptr->prefix = nullptr;
     if (fwgpu_parse_prefix_create(ptr->parser, ptr->cached_text.data(), ptr->cached_text.size(), &ptr->prefix) != FWGPU_OK) return kExceptionErrorCode;
     SharedModel &m = *ptr->model;
-    // (a packed regressor keeps no device-side context cache: the whole context + candidate record is scored -- unless --packed_context_cache)
-    if (m.re->cfg.ffm_k != 0 && m.re->packed() && m.re->packed_caches) {
+    // (a packed regressor keeps no device-side context cache: the whole context + candidate record is scored -- unless --packed_context_cache or,
+    // on a model with a deep head, --packed_head_requests)
+    if (m.re->cfg.ffm_k != 0 && m.re->packed() && m.re->keeps_packed_caches()) {
         // the cache from the packed table; no record cover (record batches with a cache are not served on packed weights): delta_ok stays false
         float label, imp;
         std::lock_guard<std::mutex> g(m.mu);
@@ -374,7 +389,8 @@ int fwgpu_predictor_predict_batch(FfiPredictor *ptr, const char *const *inputs, 
     // (--packed_context_cache: the entry route always -- a packed regressor's cache knows no record)
     bool by_record = cached && !m.re->packed() && !std::getenv("FWGPU_SERVING_ENTRY_ROUTE");
     // --packed_weights on a model with a deep head: the head-input kernel of the packed table takes entry batches only (head_packed.hip), so every line
-    // is translated here, whole, and nothing is filtered (such a predictor keeps no context cache)
+    // is translated here, whole, and nothing is filtered (such a predictor keeps no context cache -- with --packed_head_requests it has one, and a
+    // cached call takes the entry route above: translated, filtered, the set of one)
     const bool whole_entries = m.re->packed() && m.re->nn.n_layers != 0;
     // ... and of those records only what the candidate adds to the context's record, which the device already holds
     // (FWGPU_SERVING_MERGED_RECORDS=1: whole context + candidate records instead)
@@ -725,10 +741,10 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
     }
     if (total > 0xffffffffull) return fail(FWGPU_ERR_RANGE, "predict_requests: more than 2^32 - 1 lines");
     SharedModel &m = *predictors[0]->model;
-    if (m.re->packed() && !m.re->packed_caches)
+    if (m.re->packed() && !m.re->keeps_packed_caches())
         return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a --packed_weights predictor keeps no device cache") + kSee);
     if (m.re->cfg.ffm_k == 0) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a model without an FFM block keeps no device cache") + kSee);
-    if (m.re->nn.n_layers && !m.re->head_requests) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
+    if (m.re->nn.n_layers && !m.re->serves_head_requests()) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
     std::vector<const fwgpu_block_cache *> caches;  // the set: every predictor's cache once
     std::vector<uint32_t> cache_of_request(n_requests);
     for (uint32_t r = 0; r < n_requests; r++) {
@@ -845,7 +861,7 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
     const bool head = m.re->nn.n_layers != 0;
     for (unsigned t = 0, ex0 = 0; t < T; t++) {  // (labels, importances and combo slots are not read by a predict-only launch of a model without a deep head)
         const HostBatch &src = host->parts[t]->hb;
-        if (head) {  // --head_requests: the head's input keeps one LR sum per combo slot, and head_step reads {label, importance}
+        if (head) {  // --head_requests, --packed_head_requests: the head's input keeps one LR sum per combo slot, and head_step reads {label, importance}
             up(eb->lr_combo + lb[t], src.lr_combo.data(), src.lr_combo.size() * sizeof(uint16_t));
             up(eb->label + ex0, src.label.data(), src.label.size() * 4);
             up(eb->importance + ex0, src.importance.data(), src.importance.size() * 4);

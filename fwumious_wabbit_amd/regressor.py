@@ -584,6 +584,19 @@ class Regressor:
         check(self.L.fwgpu_head_requests_state(self.h, C.byref(on)))
         return bool(on.value)
 
+    def enable_packed_head_requests(self):
+        """one-way switch on a PACKED regressor with a deep head (new_regressor_from_filename(packed=True, packed_head=True)): setup_cache builds
+        caches from the 16-bit table, Batch.set_cache / set_caches on entry batches are accepted, and a predict-only launch of such a batch forms
+        every candidate's head input from its cache and its own few rows of buckets (csrc/requests_head.hip) before the layers; a batch without a
+        cache scores whole examples as before -- fwgpu_packed_enable_head_requests"""
+        check(self.L.fwgpu_packed_enable_head_requests(self.h))
+
+    def packed_head_requests_state(self) -> bool:
+        """whether enable_packed_head_requests was called -- fwgpu_packed_head_requests_state"""
+        on = C.c_int32(0)
+        check(self.L.fwgpu_packed_head_requests_state(self.h, C.byref(on)))
+        return bool(on.value)
+
     def enable_fused_head(self):
         """one-way switch on a regressor with a deep head (f32 or packed): predict-only HOGWILD batches of any size take the batched head route, and slabs up to
         the measured crossover run the whole head in one launch, activations in LDS (csrc/head_fused.hip) -- fwgpu_enable_fused_head"""

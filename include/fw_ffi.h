@@ -18,7 +18,13 @@
  *                                                         fwgpu_predictor_predict_requests serve such a model
  *                                                         (fwgpu_enable_head_requests); `--fused_head` (ours, under the
  *                                                         same two conditions) runs such a model's head in one launch for
- *                                                         small batches (fwgpu_enable_fused_head).  NULL +
+ *                                                         small batches (fwgpu_enable_fused_head);
+ *                                                         `--packed_head_requests` (ours, only with --packed_weights on
+ *                                                         a model with a deep head, else an error) gives such a predictor
+ *                                                         device context caches built from the packed table and lets the
+ *                                                         cached calls and fwgpu_predictor_predict_requests score filtered
+ *                                                         candidates (fwgpu_packed_enable_head_requests); without it the
+ *                                                         predictor scores whole lines.  NULL +
  *                                                         fwgpu_last_error() on failure (the reference panics).
  *   lib.rs:187-205  clone_lite(prototype)                 cheap per-thread copy sharing the weights
  *   lib.rs:207-212  fw_predict(ptr, vw_text)              -> prediction, or -1.0 for EOF / a line that does not parse
@@ -64,7 +70,7 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint
  * host's worker threads; one entry batch with a cache per example follows (fwgpu_batch_set_caches), whose kernel's work per candidate
  * follows the candidate's own features.  FWGPU_ERR_INVALID, pointing to fwgpu_predictor_predict_batch: predictors of different
  * models, a predictor without a device cache (no fw_setup_cache yet, --packed_weights without --packed_context_cache, a model without an FFM block), a model with
- * a deep head whose predictor was created without --head_requests.  Concurrent callers are not coalesced: each call is one launch under the model's mutex. */
+ * a deep head whose predictor was created without --head_requests (with --packed_weights: without --packed_head_requests).  Concurrent callers are not coalesced: each call is one launch under the model's mutex. */
 int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs,
                                      const uint32_t *n_inputs, float *const *out);
 

@@ -231,7 +231,7 @@ int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *cache);
  * next launch.  Like every change of a batch's contents, the call must not overlap a launch of the batch that is still in flight.
  * n_caches == 0 detaches; fwgpu_batch_set_cache on the same batch replaces the set, and the other way round.
  * FWGPU_ERR_INVALID, the batch left as it was: a record batch, an index >= n_caches, a cache of another regressor, a regressor with
- * a deep head (without fwgpu_enable_head_requests) or packed weights (without fwgpu_packed_enable_caches), a stale cache of a packed regressor, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
+ * a deep head (without fwgpu_enable_head_requests) or packed weights (without fwgpu_packed_enable_caches), both (without fwgpu_packed_enable_head_requests), a stale cache of a packed regressor, a batch with an oversize example, ffm_k % 4 != 0, an FFM row off the 16-byte boundary.  A launch
  * whose min(fields, largest FFM entry count of an example) * F * k floats exceed the 160 KiB LDS returns FWGPU_ERR_RANGE. */
 int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches,
                            const uint32_t *cache_of_example /* [examples of b] */);
@@ -607,11 +607,12 @@ int fwgpu_debug_last_route(const fwgpu_regressor *r, int *route);
 #define FWGPU_KERNEL_HEAD_REQUESTS 6 /* the head-input kernels of the requests route on a model with a deep head (fwgpu_enable_head_requests); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_KERNEL_HEAD_FUSED 7 /* the whole deep head in one launch (fwgpu_enable_fused_head, csrc/head_fused.hip), recorded AFTER the launch that formed the head inputs: [6] = 512, [7] = LDS bytes, the rest 0 */
 #define FWGPU_KERNEL_PACKED_HEAD 8 /* the head-input kernel of a packed regressor with a deep head (FWGPU_ROUTE_PACKED_HEAD): [1] = ceil(R / 256), [6] = 256, [7] = LDS bytes, [2]..[5] = 0 */
+#define FWGPU_KERNEL_PACKED_HEAD_REQUESTS 9 /* the head-input kernels of the requests route on a PACKED regressor with a deep head (fwgpu_packed_enable_head_requests); the fields as FWGPU_KERNEL_REQUESTS */
 #define FWGPU_LAUNCH_INFO_LEN 8
 int fwgpu_debug_last_launch(const fwgpu_regressor *r, int32_t *out, uint32_t n);
 /* The head inputs x = [per-combo LR sums | triangle of the FFM pair outputs] (n examples x X floats, example-major) that the last batched head predict
  * launch left on the device: the first n_floats of them to `out`.  FWGPU_ERR_INVALID unless the last batch launch took FWGPU_ROUTE_HEAD_BATCHED, FWGPU_ROUTE_PACKED_HEAD
- * or, on a model with a deep head, FWGPU_ROUTE_REQUESTS (fwgpu_enable_head_requests); FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */
+ * or, on a model with a deep head, FWGPU_ROUTE_REQUESTS (fwgpu_enable_head_requests, fwgpu_packed_enable_head_requests); FWGPU_ERR_RANGE beyond n * X.  Waits for the device. */
 int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats);
 /* an f32 as serde_json / ryu prints it in the embedded JSON documents ("0.1", "1.0", "1e-7"); NUL-terminated */
 int fwgpu_debug_format_f32(float v, char *buf, uint32_t cap);
@@ -860,7 +861,8 @@ int fwgpu_model_load_packed(const char *path, int device, fwgpu_vwmap **vw, fwgp
  * any size and in both modes, takes FWGPU_ROUTE_PACKED_HEAD (csrc/head_packed.hip forms the head's inputs from the buckets, then the
  * layers; fwgpu_enable_fused_head is accepted).  On it record batches, fwgpu_pack_regressor (from or into it),
  * fwgpu_packed_apply_diff, fwgpu_packed_enable_caches and fwgpu_enable_head_requests return FWGPU_ERR_INVALID with a message that
- * names the head, as does a shape whose field sums do not fit the CU's LDS.  The shapes refused at the load are those above. */
+ * names the head, as does a shape whose field sums do not fit the CU's LDS.  The shapes refused at the load are those above.
+ * fwgpu_packed_enable_head_requests (below) is the switch that gives such a regressor context caches and the requests route. */
 int fwgpu_model_load_packed_head(const char *path, int device, fwgpu_vwmap **vw, fwgpu_model_instance **mi, fwgpu_regressor **r);
 /* How the FFM weight table lives on the device, and the bytes it occupies there */
 enum { FWGPU_FFM_F32 = 0, FWGPU_FFM_F16_BUCKETS = 1 };
@@ -893,6 +895,25 @@ int fwgpu_packed_caches_state(const fwgpu_regressor *r, int *enabled, uint64_t *
  * (min(fields, largest FFM entry count) * F * k + F (F + 1) / 2) floats exceed the 160 KiB LDS. */
 int fwgpu_enable_head_requests(fwgpu_regressor *r);
 int fwgpu_head_requests_state(const fwgpu_regressor *r, int *enabled);
+/* ---- context caches and the requests route on a PACKED regressor with a deep head (opt-in).  fwgpu_packed_enable_head_requests is a ONE-WAY switch
+ * on a regressor made by fwgpu_model_load_packed_head from a model with a deep head.  FWGPU_ERR_INVALID with the reason: an f32 regressor (with or
+ * without a head), a packed regressor without a head, ffm_k == 0, ffm_k % 4 != 0, more than 256 fields.  fwgpu_packed_enable_caches and
+ * fwgpu_enable_head_requests refuse such a regressor before and after it, with the messages they always had.  Without the switch nothing changes:
+ * routes, refusals and messages are those above.  With it, on that regressor:
+ *   fwgpu_setup_cache          builds the cache from the buckets with the packed build kernel (csrc/requests.hip), under the regressor's weights epoch
+ *   fwgpu_batch_set_caches     a cache per example of an ENTRY batch; fwgpu_batch_set_cache: the set of one.  A predict-only launch of such a batch
+ *                              takes FWGPU_ROUTE_REQUESTS with the kernel family FWGPU_KERNEL_PACKED_HEAD_REQUESTS and the launch shape of
+ *                              FWGPU_KERNEL_HEAD_REQUESTS: every cache's triangle row, one wavefront per candidate that gathers its own rows as
+ *                              8-byte loads of four buckets (csrc/requests_head.hip), then the layers.  x has the bits fwgpu_enable_head_requests
+ *                              gives on an f32 regressor that holds the dequantised values, and is the same between launches, modes and
+ *                              candidate orders; fwgpu_debug_head_inputs serves it
+ *   fwgpu_predict_with_cache   the same route for one example
+ *   a batch without a cache    FWGPU_ROUTE_PACKED_HEAD, as before the switch and with the same bits
+ * Still FWGPU_ERR_INVALID: update != 0 ("predict-only"), record batches, an oversize example, a hash off the 4-bucket boundary, a foreign cache, an
+ * index >= n_caches, a stale cache; fwgpu_block_cache_cover_record, fwgpu_packed_apply_diff and fwgpu_pack_regressor as on every packed regressor with
+ * a deep head.  FWGPU_ERR_RANGE: the LDS bound of fwgpu_enable_head_requests. */
+int fwgpu_packed_enable_head_requests(fwgpu_regressor *r);
+int fwgpu_packed_head_requests_state(const fwgpu_regressor *r, int *enabled);
 /* ---- the deep head's predict-only forward in one launch, for small serving batches (opt-in).  fwgpu_enable_fused_head is a ONE-WAY switch on a
  * regressor with a deep head, whether its FFM table is f32 or packed (fwgpu_model_load_packed_head: the head's own tables are f32 either way);
  * FWGPU_ERR_INVALID with the reason for a regressor without a head.  Without it nothing changes route or bits.  With it:
@@ -915,8 +936,8 @@ int fwgpu_debug_head_forward_time(fwgpu_regressor *r, uint32_t n, int fused, uin
 /* debug: a cache's contents as the device holds them -- T [F * F * k], dcf [F], cnt [F], the epoch it was set up at (each may be NULL).  Waits for the device. */
 int fwgpu_debug_block_cache_read(const fwgpu_block_cache *cache, float *T, float *dcf, uint32_t *cnt, uint64_t *epoch);
 /* debug (scripts/bench_serving_packed_requests.py): milliseconds per launch, by device events over `reps` launches on the null stream, of the
- * requests route of a batch with a set attached (base kernel + predict kernel).  rows: the packed predict kernel's rows in flight per lane, 4 or 8,
- * 0 = the default (the only value an f32 regressor takes). */
+ * requests route of a batch with a set attached (base kernel + predict kernel; on a model with a deep head: base kernel + head-input kernel + the
+ * layers).  rows: the packed predict or head-input kernel's rows in flight per lane, 4 or 8, 0 = the default (the only value an f32 regressor takes). */
 int fwgpu_debug_requests_time(fwgpu_regressor *r, fwgpu_batch *b, int rows, uint32_t reps, float *ms_per_launch);
 /* ---- quantising on the device: train -> publish -> serve without the training blob crossing to the host
  * The reference's quantiser (quantization.rs:18-80) as HIP kernels (csrc/quantize.hip): a statistics pass (min, max, "a weight is not finite")
