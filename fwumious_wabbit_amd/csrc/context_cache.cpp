@@ -281,13 +281,20 @@ int fwgpu_batch_set_cache(fwgpu_batch *b, const fwgpu_block_cache *c) {
 // (requests.hip: FWGPU_ROUTE_REQUESTS).  The pointer table and the index array are copied here; the caches are referenced and must
 // outlive the launches (a cache refilled by fwgpu_setup_cache on the same handle is read as refilled).  n_caches == 0 detaches.
 // A refused call leaves the batch as it was.
+static int set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches, const uint32_t *cache_of_example,
+                      const uint32_t *d_cache_of_example, hipStream_t d_stream);
 int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches, const uint32_t *cache_of_example) {
+    return set_caches(b, caches, n_caches, cache_of_example, nullptr, nullptr);
+}
+// cache_of_example: the index array on the host, checked here -- or NULL and d_cache_of_example: on the device already (batch_set_caches_device)
+static int set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches, const uint32_t *cache_of_example,
+                      const uint32_t *d_cache_of_example, hipStream_t d_stream) {
     if (!b) return fail(FWGPU_ERR_INVALID, "NULL batch");
     if (n_caches == 0) {
         requests_detach(b);
         return FWGPU_OK;
     }
-    if (!caches || (b->n && !cache_of_example)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (!caches || (b->n && !cache_of_example && !d_cache_of_example)) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if (!b->owner) return fail(FWGPU_ERR_INVALID, "set_caches: the batch has no regressor");
     if (const char *why = requests_refusal(b->owner, b)) return fail(FWGPU_ERR_INVALID, std::string("set_caches: ") + why);
     for (uint32_t c = 0; c < n_caches; c++) {
@@ -295,7 +302,7 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
         if (caches[c]->owner != b->owner) return fail(FWGPU_ERR_INVALID, "set_caches: a cache belongs to another regressor");
         if (cache_is_stale(b->owner, caches[c])) return fail(FWGPU_ERR_INVALID, std::string("set_caches: ") + kStaleCache);
     }
-    for (uint32_t i = 0; i < b->n; i++)
+    for (uint32_t i = 0; cache_of_example && i < b->n; i++)
         if (cache_of_example[i] >= n_caches) return fail(FWGPU_ERR_INVALID, "set_caches: cache_of_example holds an index >= n_caches");
     // one allocation: d_T of every cache, d_dcf of every cache, base [n_caches] (8-byte slots), then cache_of [n]
     // (a deep head, fwgpu_enable_head_requests: base holds every cache's triangle row, F (F + 1) / 2 floats each)
@@ -307,7 +314,7 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
         tp[c] = caches[c]->d_T;
         tp[n_caches + c] = caches[c]->d_dcf;
     }
-    if (b->n) memcpy(host.data() + table + base, cache_of_example, (size_t)b->n * sizeof(uint32_t));
+    if (b->n && cache_of_example) memcpy(host.data() + table + base, cache_of_example, (size_t)b->n * sizeof(uint32_t));
     FWGPU_HIP(hipSetDevice(b->owner->device));
     // (a set that fits the allocation of the one it replaces is written over it: the call must not overlap a launch of this batch that is still in
     // flight, as with every other change of a batch's contents)
@@ -317,7 +324,12 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
         (void)hipGetLastError();
         return fail(FWGPU_ERR_OOM, "set_caches: no device memory for the cache table");
     }
-    if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    bool copied = hipMemcpy(dev, host.data(), cache_of_example ? host.size() : table + base, hipMemcpyHostToDevice) == hipSuccess;
+    if (copied && !cache_of_example && b->n)
+        copied = hipMemcpyAsync(static_cast<unsigned char *>(dev) + table + base, d_cache_of_example, (size_t)b->n * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                d_stream) == hipSuccess &&
+                 hipStreamSynchronize(d_stream) == hipSuccess;
+    if (!copied) {
         if (fresh) (void)hipFree(dev);
         return fail(FWGPU_ERR_DEVICE, "set_caches: copy to the device failed");
     }
@@ -335,6 +347,15 @@ int fwgpu_batch_set_caches(fwgpu_batch *b, const fwgpu_block_cache *const *cache
     b->req_caches.assign(caches, caches + n_caches);
     return FWGPU_OK;
 }
+
+}  // extern "C"
+namespace fwgpu {
+int batch_set_caches_device(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches, const uint32_t *d_cache_of_example, hipStream_t stream) {
+    if (!b || !n_caches || !d_cache_of_example) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    return set_caches(b, caches, n_caches, nullptr, d_cache_of_example, stream);
+}
+}  // namespace fwgpu
+extern "C" {
 
 // ONE cache for every example of an entry batch of a packed regressor: the set of one.  The table of the call before is kept where it still says the
 // same (the single-example calls attach the same cache request after request).

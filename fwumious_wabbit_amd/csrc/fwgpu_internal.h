@@ -803,6 +803,9 @@ int check_translator(const fwgpu_regressor *r, const fwgpu_translator_config *t)
 // validates one record against the translator and counts the entries its translation produces
 int count_record(const fwgpu_translator_config *t, const uint32_t *rec, uint32_t rec_len, uint32_t *n_lr, uint32_t *n_ffm);
 int block_cache_record_ok(const fwgpu_block_cache *c, const fwgpu_translator_config *t, const uint32_t *record, uint32_t len, bool delta);
+// fwgpu_batch_set_caches with the index array already on the device: d_cache_of_example [b->n], every index below n_caches (the caller's kernels wrote
+// them); copied on `stream`, which the call waits for
+int batch_set_caches_device(fwgpu_batch *b, const fwgpu_block_cache *const *caches, uint32_t n_caches, const uint32_t *d_cache_of_example, hipStream_t stream);
 // the same for a candidate-only record on top of its context's record (ctx may be NULL)
 int count_record(const fwgpu_translator_config *t, const uint32_t *rec, uint32_t rec_len, const uint32_t *ctx, uint32_t ctx_len,
                  uint32_t *n_lr, uint32_t *n_ffm);
@@ -818,6 +821,20 @@ struct TextLines {
 int text_lines_scan(fwgpu_text_parser *tp, const fwgpu_parse_prefix *px, const fwgpu_block_cache *cache, const fwgpu_translator_config *t,
                     const char *text, uint64_t len, uint64_t piece_bytes, bool zero_word1, TextLines *out);
 int text_lines_place(fwgpu_text_parser *tp, uint32_t *d_records);
+// Many requests' lines (text_parser.cpp): ONE plain pass over `text` (ends in a newline, at most text_device_max_bytes()) whose line index, statuses,
+// record offsets and records (word 1 zeroed) stay on the device, enqueued on `stream`; they live until the parser's next call
+struct TextDeviceLines {
+    const unsigned char *text = nullptr;
+    const uint32_t *lstart = nullptr;   // [nlines + 1]
+    const uint4 *status = nullptr;      // [nlines] textparse.h
+    const uint32_t *records = nullptr;
+    const uint64_t *rec_off = nullptr;  // [nlines + 1]
+    uint32_t nlines = 0;
+    hipStream_t stream = nullptr;
+};
+uint64_t text_device_max_bytes();
+uint32_t text_parser_namespaces(const fwgpu_text_parser *tp);
+int text_lines_device(fwgpu_text_parser *tp, const char *text, uint32_t len, TextDeviceLines *out);
 // Training from text (text_parser.cpp; driven by trainer.cpp fwgpu_trainer_digest_text_device).  text_train_begin: once per call, the translator's
 // arrays go up for the status pass's entry counts.  text_train_piece: one piece of text (whole lines; more than 16 MiB only as ONE line) is parsed and
 // planned on the device (textparse.hip text_batch_plan) and its records are placed in the parser's buffer set `set` (0 / 1) -- the caller has retired

@@ -45,6 +45,8 @@
 
 #include "fw_ffi.h"
 #include "fwgpu_internal.h"
+#include "requests_text.h"
+#include "textparse.h"
 
 using namespace fwgpu;
 
@@ -60,7 +62,15 @@ struct SharedModel {  // what clone_lite shares: the immutable regressor and the
     fwgpu_batch *one = nullptr;    // single requests: a host-mapped batch (no copy calls, no memset: launch + one synchronisation)
     fwgpu_text_parser *tp = nullptr;  // fwgpu_predictor_predict_text: the device parser, made by the first call, used under mu
     fwgpu_batch *requests = nullptr;  // fwgpu_predictor_predict_requests: its entry batch, grown on demand and reused (n_cap examples)
+    // fwgpu_predictor_predict_requests_text: the translator's arrays on the device (as an empty record batch holds them), what its kernels write
+    // between the passes, and what every call uploads (the requests' offsets, the caches of the set); grown on demand and reused
+    fwgpu_batch *rt_tr = nullptr;
+    void *rt_scratch = nullptr, *rt_side = nullptr;
+    size_t rt_scratch_bytes = 0, rt_side_bytes = 0;
     ~SharedModel() {
+        if (rt_scratch) (void)hipFree(rt_scratch);
+        if (rt_side) (void)hipFree(rt_side);
+        if (rt_tr) fwgpu_batch_free(rt_tr);
         if (tp) fwgpu_text_parser_free(tp);
         if (requests) fwgpu_batch_free(requests);
         if (batch) fwgpu_batch_free(batch);
@@ -146,6 +156,11 @@ struct FfiPredictor {
     std::vector<fwgpu_ffm_entry> ffm;
     std::vector<fwgpu_lr_entry> ctx_lr;    // --packed_context_cache: the context's entries as fw_setup_cache translated them: what a stale cache
     std::vector<fwgpu_ffm_entry> ctx_ffm;  // is rebuilt from (lr / ffm above are scratch of every request)
+    std::vector<uint32_t> ctx_record;      // fwgpu_predictor_predict_requests_text: the context's own record, when the scanned context is that record
+    // ... and what its kernels read of this predictor's cache, as it is uploaded: present keys | 64 filter words | the record | cover bits (each part
+    // 8-byte aligned; the byte offsets of the last three); built by the first text call after fw_setup_cache (rt_piece_of), empty before
+    std::vector<uint64_t> rt_piece;
+    size_t rt_piece_bits = 0, rt_piece_rec = 0, rt_piece_cover = 0;
     uint64_t text_lines = 0, text_host_lines = 0;  // fwgpu_predictor_last_text_route
     int text_fell_back = 0;
     ~FfiPredictor() {
@@ -339,6 +354,9 @@ float fw_setup_cache(FfiPredictor *ptr, const char *input_buffer) {  // lib.rs:2
     if (ptr->prefix) fwgpu_parse_prefix_free(ptr->prefix);
     ptr->prefix = nullptr;
     if (fwgpu_parse_prefix_create(ptr->parser, ptr->cached_text.data(), ptr->cached_text.size(), &ptr->prefix) != FWGPU_OK) return kExceptionErrorCode;
+    ptr->rt_piece.clear();
+    ptr->ctx_record.clear();  // (kept for every kind of cache: a packed regressor's cache knows no record of its own)
+    if (fwgpu_parse_prefix_is_record(ptr->prefix, ptr->record.data(), n_words)) ptr->ctx_record.assign(ptr->record.begin(), ptr->record.begin() + n_words);
     SharedModel &m = *ptr->model;
     // (a packed regressor keeps no device-side context cache: the whole context + candidate record is scored -- unless --packed_context_cache or,
     // on a model with a deep head, --packed_head_requests)
@@ -723,6 +741,35 @@ int fwgpu_predictor_predict_text(FfiPredictor *ptr, const char *text, uint64_t l
     return FWGPU_OK;
 }
 
+// fwgpu_predictor_predict_requests_text: the refusals of fwgpu_predictor_predict_requests, with its messages, and the set (every predictor's cache once)
+static int requests_set_of(FfiPredictor *const *predictors, uint32_t n_requests, std::vector<const fwgpu_block_cache *> &caches,
+                           std::vector<uint32_t> &cache_of_request) {
+    static const char *kSee = " (fwgpu_predictor_predict_batch serves this predictor, one request per call)";
+    for (uint32_t r = 0; r < n_requests; r++) {
+        if (!predictors[r]) return fail(FWGPU_ERR_INVALID, "NULL argument");
+        if (predictors[r]->model != predictors[0]->model)
+            return fail(FWGPU_ERR_INVALID, std::string("predict_requests: the predictors are not the prototype and clone_lite copies of ONE model") + kSee);
+    }
+    SharedModel &m = *predictors[0]->model;
+    if (m.re->packed() && !m.re->keeps_packed_caches())
+        return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a --packed_weights predictor keeps no device cache") + kSee);
+    if (m.re->cfg.ffm_k == 0) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a model without an FFM block keeps no device cache") + kSee);
+    if (m.re->nn.n_layers && !m.re->serves_head_requests()) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: models with a deep head are not served by the requests route") + kSee);
+    caches.clear();
+    cache_of_request.assign(n_requests, 0);
+    for (uint32_t r = 0; r < n_requests; r++) {
+        const FfiPredictor *p = predictors[r];
+        if (!p->cache || !p->prefix) return fail(FWGPU_ERR_INVALID, std::string("predict_requests: a predictor has no device cache (no fw_setup_cache yet)") + kSee);
+        size_t c = 0;
+        while (c < caches.size() && caches[c] != p->cache) c++;
+        if (c == caches.size()) caches.push_back(p->cache);
+        cache_of_request[r] = (uint32_t)c;
+    }
+    return FWGPU_OK;
+}
+static const char *const kRequestsTooManyEntries =
+    "predict_requests: a line has more than 4096 entries of a kind (fwgpu_predictor_predict_batch serves this predictor, one request per call)";
+
 // The candidates of SEVERAL requests in one launch: predictors[r] (the prototype and clone_lite copies of one model, each after its own
 // fw_setup_cache; the same one may appear twice) with its lines inputs[r][0 .. n_inputs[r]).  The existing entry route per line -- parse after the
 // context's prefix, translate, filter by the cache's features -- with the requests spread over the worker pool, then ONE shared entry batch with a cache
@@ -887,6 +934,291 @@ int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n
     if (rc != FWGPU_OK) return rc;
     for (uint32_t i = 0; i < nrec; i++) out[ex_req[i]][ex_line[i]] = preds[i];
     return FWGPU_OK;
+}
+
+// fwgpu_predictor_predict_requests_text by the existing route: every request's lines, each with its newline, through fwgpu_predictor_predict_requests
+static int predict_requests_text_by_lines(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *texts, const uint64_t *lens,
+                                          float *const *out, const uint64_t *caps, uint64_t *n_lines) {
+    std::vector<std::vector<std::string>> lines(n_requests);
+    uint64_t total = 0;
+    bool fits = true;
+    for (uint32_t r = 0; r < n_requests; r++) {
+        for (uint64_t pos = 0; pos < lens[r];) {
+            const char *e = static_cast<const char *>(std::memchr(texts[r] + pos, '\n', lens[r] - pos));
+            const uint64_t size = e ? (uint64_t)(e - (texts[r] + pos)) + 1 : lens[r] - pos;
+            lines[r].emplace_back(texts[r] + pos, size);
+            if (!e) lines[r].back().push_back('\n');
+            pos += size;
+        }
+        n_lines[r] = lines[r].size();
+        total += lines[r].size();
+        fits = fits && lines[r].size() <= caps[r] && lines[r].size() <= 0xffffffffull;
+    }
+    predictors[0]->text_lines = predictors[0]->text_host_lines = total;
+    predictors[0]->text_fell_back = 1;
+    if (!fits) return fail(FWGPU_ERR_RANGE, "predict_requests_text: more lines than a request's output holds");
+    std::vector<std::vector<const char *>> ptrs(n_requests);
+    std::vector<const char *const *> inputs(n_requests);
+    std::vector<uint32_t> n_inputs(n_requests);
+    for (uint32_t r = 0; r < n_requests; r++) {
+        for (const std::string &l : lines[r]) ptrs[r].push_back(l.c_str());
+        inputs[r] = ptrs[r].data();
+        n_inputs[r] = (uint32_t)ptrs[r].size();
+    }
+    return fwgpu_predictor_predict_requests(predictors, n_requests, inputs.data(), n_inputs.data(), out);
+}
+
+// The predictor's piece of the text call's upload, made once per fw_setup_cache.  false: the scanned context is not its own record, or the record is
+// not one the kernels may read by what its slot words say (every range inside it, behind the slots, of whole {hash, value} pairs).
+static bool rt_piece_of(FfiPredictor *p, uint32_t nns) {
+    if (!p->rt_piece.empty()) return true;
+    const std::vector<uint32_t> &rec = p->ctx_record;
+    if (rec.size() < 3 + (size_t)nns || rec.size() > kRtMaxRecord) return false;
+    for (uint32_t ns = 0; ns < nns; ns++) {
+        const uint32_t w = rec[3 + ns], st = (w >> 16) & 0x3fffu, en = w & 0xffffu;
+        if ((w & 0x80000000u) && w != 0x80000000u && !(en <= rec.size() && en >= st && st >= 3 + nns && !((en - st) & 1u))) return false;
+    }
+    const std::vector<uint64_t> &present = p->cache->present;
+    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+    p->rt_piece_bits = 8 * present.size();
+    p->rt_piece_rec = p->rt_piece_bits + 8 * 64;
+    p->rt_piece_cover = up8(p->rt_piece_rec + 4 * rec.size());
+    p->rt_piece.assign(up8(p->rt_piece_cover + 4 * (((size_t)nns + 31) / 32)) / 8, 0);
+    unsigned char *b = reinterpret_cast<unsigned char *>(p->rt_piece.data());
+    if (!present.empty()) std::memcpy(b, present.data(), 8 * present.size());
+    uint64_t *bits = reinterpret_cast<uint64_t *>(b + p->rt_piece_bits);
+    for (uint64_t key : present) {  // (context_cache.cpp present_bit)
+        const uint32_t h = (uint32_t)((key * 0x9e3779b97f4a7c15ULL) >> 52);
+        bits[h >> 6] |= 1ull << (h & 63);
+    }
+    std::memcpy(b + p->rt_piece_rec, rec.data(), 4 * rec.size());
+    uint32_t *cover = reinterpret_cast<uint32_t *>(b + p->rt_piece_cover);
+    for (uint32_t ns = 0; ns < nns; ns++)
+        if (rec[3 + ns] != 0x80000000u) cover[ns >> 5] |= 1u << (ns & 31);  // NO_FEATURES (parser.rs:19)
+    return true;
+}
+
+// device memory kept between calls: grown (never shrunk) to `bytes`
+static int rt_grow(void **p, size_t *cap, size_t bytes) {
+    if (bytes <= *cap) return FWGPU_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const size_t want = bytes + bytes / 2 + 256;
+    FWGPU_HIP(hipMalloc(p, want));
+    *cap = want;
+    return FWGPU_OK;
+}
+
+// The candidates of SEVERAL requests from their TEXT, a candidate per line, without the host's parser, translator or filter: ONE plain pass of the
+// device parser over all texts (text_lines_device), the count / scan / emit kernels of requests_text.hip -- which decide the cache's record rule per
+// line against the line's OWN request's cache and write the filtered entries in the host translator's order straight into the entry batch -- and the
+// ONE launch fwgpu_predictor_predict_requests makes.  The host reads one small block (totals, maxima, the flag, every request's first line) and the
+// predictions.  The whole call goes through fwgpu_predictor_predict_requests on the split lines instead (fell_back) when any line is not the device
+// parser's, does not start with '|', fills a namespace its context fills or repeats a cached FFM feature; when a predictor's scanned context is not its
+// own record; with FWGPU_SERVING_HOST_PARSE; with a namespace map beyond the device parser's; and with more text than one parser pass takes.
+int fwgpu_predictor_predict_requests_text(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *texts, const uint64_t *lens,
+                                          float *const *out, const uint64_t *caps, uint64_t *n_lines) {
+    if (n_requests == 0) return FWGPU_OK;
+    if (!predictors || !texts || !lens || !out || !caps || !n_lines) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    uint64_t total_len = 0;
+    for (uint32_t r = 0; r < n_requests; r++) {
+        if (!predictors[r] || (lens[r] && !texts[r]) || (caps[r] && !out[r])) return fail(FWGPU_ERR_INVALID, "NULL argument");
+        n_lines[r] = 0;
+        total_len += lens[r] + (lens[r] && texts[r][lens[r] - 1] != '\n' ? 1 : 0);
+    }
+    std::vector<const fwgpu_block_cache *> caches;
+    std::vector<uint32_t> cache_of_request;
+    if (const int rc0 = requests_set_of(predictors, n_requests, caches, cache_of_request)) return rc0;
+    FfiPredictor *host = predictors[0];
+    host->text_lines = host->text_host_lines = 0;
+    host->text_fell_back = 0;
+    if (total_len == 0) return FWGPU_OK;
+    SharedModel &m = *host->model;
+    auto by_lines = [&]() { return predict_requests_text_by_lines(predictors, n_requests, texts, lens, out, caps, n_lines); };
+    if (std::getenv("FWGPU_SERVING_HOST_PARSE") || total_len > std::min<uint64_t>(0xffffffffull, text_device_max_bytes())) return by_lines();
+    std::vector<FfiPredictor *> owner(caches.size(), nullptr);  // the predictor that holds each cache of the set (and its context's record)
+    for (uint32_t r = 0; r < n_requests; r++) owner[cache_of_request[r]] = predictors[r];
+    std::unique_lock<std::mutex> g(m.mu);
+    int rc = FWGPU_OK;
+    if (!m.tp && (rc = fwgpu_text_parser_create(m.vw, m.re->device, &m.tp)) != FWGPU_OK) return rc;
+    if (!m.rt_tr && (rc = record_batch_alloc(m.re, &m.tr, 1, 16, &m.rt_tr)) != FWGPU_OK) return rc;
+    const DevTranslator dtr = m.rt_tr->tr;  // (made once per model and never changed)
+    const uint32_t nns = text_parser_namespaces(m.tp);
+    g.unlock();  // ---- the host's share of the call needs no device and holds up no other predictor of the model
+    bool served = nns <= kTextMaxNamespaces && requests_text_lds_bytes(dtr) != 0;
+    for (uint32_t j = 0; served && j < dtr.n_members; j++) served = m.tr.combo_ns[j] < nns;
+    for (uint32_t j = 0; served && j < dtr.n_pairs; j++) served = m.tr.field_ns[j] < nns;
+    for (size_t c = 0; served && c < owner.size(); c++) served = rt_piece_of(owner[c], nns);
+    if (!served) return by_lines();
+    // the texts back to back, each request ending in a newline
+    std::string text;
+    text.reserve((size_t)total_len);
+    std::vector<uint32_t> t_off(n_requests + 1, 0);
+    for (uint32_t r = 0; r < n_requests; r++) {
+        t_off[r] = (uint32_t)text.size();
+        if (!lens[r]) continue;
+        text.append(texts[r], (size_t)lens[r]);
+        if (text.back() != '\n') text.push_back('\n');
+    }
+    t_off[n_requests] = (uint32_t)text.size();
+    // what the kernels read beside the parse, one upload: the requests' offsets and caches, the descriptors of the set's caches, and every cache's piece
+    // (kept by its predictor since its fw_setup_cache: present keys, filter bits, the context's record, its cover bits).  An f32 cache's own device
+    // copies are not used: they cover the slots up to the last FFM namespace only, where this route's rule takes every slot the context fills, and a
+    // packed regressor's cache has none
+    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+    size_t q = 0;
+    const size_t q_toff = q; q = up8(q + 4 * ((size_t)n_requests + 1));
+    const size_t q_cor = q; q = up8(q + 4 * (size_t)n_requests);
+    const size_t q_desc = q; q = up8(q + sizeof(RtCache) * caches.size());
+    std::vector<size_t> q_piece(caches.size());
+    for (size_t c = 0; c < caches.size(); c++) {
+        q_piece[c] = q;
+        q += 8 * owner[c]->rt_piece.size();
+    }
+    std::vector<uint64_t> side((q + 7) / 8, 0);
+    unsigned char *sb = reinterpret_cast<unsigned char *>(side.data());
+    std::memcpy(sb + q_toff, t_off.data(), 4 * t_off.size());
+    std::memcpy(sb + q_cor, cache_of_request.data(), 4 * cache_of_request.size());
+    for (size_t c = 0; c < caches.size(); c++) std::memcpy(sb + q_piece[c], owner[c]->rt_piece.data(), 8 * owner[c]->rt_piece.size());
+    g.lock();
+    for (uint32_t r = 0; r < n_requests && rc == FWGPU_OK; r++) rc = refresh_stale_cache(predictors[r]);  // (--packed_context_cache)
+    if (rc != FWGPU_OK) return rc;
+    if ((rc = rt_grow(&m.rt_side, &m.rt_side_bytes, q)) != FWGPU_OK) return rc;
+    const unsigned char *db = static_cast<const unsigned char *>(m.rt_side);
+    for (size_t c = 0; c < caches.size(); c++) {  // (the descriptors point into the device copy)
+        const FfiPredictor *o = owner[c];
+        const unsigned char *piece = db + q_piece[c];
+        RtCache d{};
+        d.present = reinterpret_cast<const uint64_t *>(piece);
+        d.present_bits = reinterpret_cast<const uint64_t *>(piece + o->rt_piece_bits);
+        d.ctx_rec = reinterpret_cast<const uint32_t *>(piece + o->rt_piece_rec);
+        d.cover = reinterpret_cast<const uint32_t *>(piece + o->rt_piece_cover);
+        d.ctx_len = (uint32_t)o->ctx_record.size();
+        d.n_present = (uint32_t)(o->rt_piece_bits / 8);
+        std::memcpy(sb + q_desc + sizeof(RtCache) * c, &d, sizeof(RtCache));
+    }
+    // ---- one plain pass of the device parser
+    TextDeviceLines dl;
+    if ((rc = text_lines_device(m.tp, text.data(), (uint32_t)text.size(), &dl)) != FWGPU_OK) return rc;
+    const uint32_t n = dl.nlines;
+    size_t w = 0;
+    const size_t w_counts = w; w = up8(w + 16 * (size_t)n);
+    const size_t w_of = w; w = up8(w + 4 * (size_t)n);
+    const size_t w_tot = w; w = up8(w + sizeof(RtTotals) + 4 * ((size_t)n_requests + 1));
+    if ((rc = rt_grow(&m.rt_scratch, &m.rt_scratch_bytes, w)) != FWGPU_OK) return rc;
+    // (`side` is pageable and local: every return between this copy and the wait for the stream below waits for it first)
+    auto drained = [&](int code) {
+        (void)hipStreamSynchronize(dl.stream);
+        return code;
+    };
+    if (hipMemcpyAsync(m.rt_side, sb, q, hipMemcpyHostToDevice, dl.stream) != hipSuccess)
+        return drained(fail(FWGPU_ERR_DEVICE, "predict_requests_text: copy to the device failed"));
+    // ---- count pass and scan; the one block the host reads
+    unsigned char *wb = static_cast<unsigned char *>(m.rt_scratch);
+    RtArgs a{};
+    a.text = dl.text;
+    a.lstart = dl.lstart;
+    a.status = dl.status;
+    a.records = dl.records;
+    a.rec_off = dl.rec_off;
+    a.nlines = n;
+    a.nns = nns;
+    a.t_off = reinterpret_cast<const uint32_t *>(db + q_toff);
+    a.cache_of_request = reinterpret_cast<const uint32_t *>(db + q_cor);
+    a.caches = reinterpret_cast<const RtCache *>(db + q_desc);
+    a.n_requests = n_requests;
+    a.tr = dtr;
+    a.ffm_k = m.re->cfg.ffm_k;
+    a.has_lr = m.re->cfg.wiring != FWGPU_WIRING_FFM_ONLY;
+    a.counts = reinterpret_cast<uint4 *>(wb + w_counts);
+    a.cache_of = reinterpret_cast<uint32_t *>(wb + w_of);
+    a.totals = reinterpret_cast<RtTotals *>(wb + w_tot);
+    a.first_line = reinterpret_cast<uint32_t *>(wb + w_tot + sizeof(RtTotals));
+    std::vector<uint64_t> block((sizeof(RtTotals) + 4 * ((size_t)n_requests + 1) + 7) / 8);
+    const bool timing = std::getenv("FWGPU_SERVING_TIMING") != nullptr;  // device events around the new kernels alone, to stderr (as predict_batch's laps)
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (timing)
+        for (hipEvent_t &e : ev)
+            if (hipEventCreate(&e) != hipSuccess) return drained(fail(FWGPU_ERR_DEVICE, "predict_requests_text: no event"));
+    struct EventsGuard {
+        hipEvent_t *ev;
+        ~EventsGuard() {
+            for (int i = 0; i < 4; i++)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } events_guard{ev};
+    if (n) {
+        hipError_t e = timing ? hipEventRecord(ev[0], dl.stream) : hipSuccess;
+        if (e == hipSuccess) e = launch_requests_text_count(a, dl.stream);
+        if (e == hipSuccess && timing) e = hipEventRecord(ev[1], dl.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(block.data(), a.totals, sizeof(RtTotals) + 4 * ((size_t)n_requests + 1), hipMemcpyDeviceToHost, dl.stream);
+        if (e != hipSuccess) return drained(fail(FWGPU_ERR_DEVICE, std::string("predict_requests_text: count pass: ") + hipGetErrorString(e)));
+    }
+    FWGPU_HIP(hipStreamSynchronize(dl.stream));
+    RtTotals tot{};
+    std::memcpy(&tot, block.data(), sizeof(RtTotals));
+    const uint32_t *first_line = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(block.data()) + sizeof(RtTotals));
+    if (n == 0 || tot.fallback) {
+        g.unlock();
+        return by_lines();
+    }
+    bool fits = true;
+    for (uint32_t r = 0; r < n_requests; r++) {
+        n_lines[r] = first_line[r + 1] - first_line[r];
+        fits = fits && n_lines[r] <= caps[r];
+    }
+    host->text_lines = n;
+    if (!fits) return fail(FWGPU_ERR_RANGE, "predict_requests_text: more lines than a request's output holds");
+    if (tot.max_ffm > 4096 || tot.max_lr > 4096) return fail(FWGPU_ERR_INVALID, kRequestsTooManyEntries);
+    // ---- the entry batch, filled by the emit pass; the set with the index array the count pass left; the launch of fwgpu_predictor_predict_requests
+    if (!m.requests || m.requests->n_cap < n || m.requests->n_lr < tot.tot_lr || m.requests->n_ffm < tot.tot_ffm) {
+        if (m.requests) fwgpu_batch_free(m.requests);
+        m.requests = nullptr;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2ull * n, 256), 0xffffffffull);
+        if ((rc = batch_alloc(m.re, cap, std::max<uint64_t>(2 * tot.tot_lr, 1 << 16), std::max<uint64_t>(2 * tot.tot_ffm, 1 << 14), &m.requests)) != FWGPU_OK) return rc;
+        m.requests->n_cap = cap;
+    }
+    fwgpu_batch *eb = m.requests;
+    eb->n = n;
+    eb->max_lr = tot.max_lr;
+    eb->max_ffm = tot.max_ffm;
+    eb->aligned4 = (dtr.ffm_mask & 3u) == 0;  // every row starts where the translator's mask puts it
+    a.ffm_hash = eb->ffm_hash;
+    a.ffm_val = eb->ffm_val;
+    a.ffm_fld = eb->ffm_fld;
+    a.ffm_off = eb->ffm_off;
+    a.lr_hash = eb->lr_hash;
+    a.lr_val = eb->lr_val;
+    a.lr_off = eb->lr_off;
+    a.lr_combo = eb->lr_combo;
+    a.label = eb->label;
+    a.importance = eb->importance;
+    if (timing) FWGPU_HIP(hipEventRecord(ev[2], nullptr));
+    FWGPU_HIP(launch_requests_text_emit(a, nullptr));  // (the parser's stream is idle: the launch's own stream from here on)
+    if (timing) FWGPU_HIP(hipEventRecord(ev[3], nullptr));
+    rc = batch_set_caches_device(eb, caches.data(), (uint32_t)caches.size(), a.cache_of, nullptr);
+    if (rc == FWGPU_OK) rc = fwgpu_learn_batch(m.re, eb, FWGPU_MODE_HOGWILD, /*update=*/0, nullptr);
+    std::vector<float> preds(n);
+    if (rc == FWGPU_OK) rc = fwgpu_batch_predictions(eb, preds.data(), n, nullptr);
+    if (rc != FWGPU_OK) return rc;
+    if (timing) {  // (the predictions are here: every event has passed)
+        float ms_count = 0.0f, ms_emit = 0.0f;
+        FWGPU_HIP(hipEventElapsedTime(&ms_count, ev[0], ev[1]));
+        FWGPU_HIP(hipEventElapsedTime(&ms_emit, ev[2], ev[3]));
+        std::fprintf(stderr, "[predict_requests_text] %u requests, %u lines: count + scan %.4f ms, emit %.4f ms\n", n_requests, n, ms_count, ms_emit);
+    }
+    for (uint32_t r = 0; r < n_requests; r++)
+        if (n_lines[r]) std::memcpy(out[r], preds.data() + first_line[r], 4 * (size_t)n_lines[r]);
+    return FWGPU_OK;
+}
+
+// which path and kernel the model's regressor took in its last batch launch (fwgpu_debug_last_route, fwgpu_debug_last_launch): the prototype and its
+// clone_lite copies share the regressor, so this is the last launch of any of them
+int fwgpu_predictor_last_launch(const FfiPredictor *ptr, int *route, int32_t *launch, uint32_t n) {
+    if (!ptr || !route || (n && !launch)) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    const int rc = fwgpu_debug_last_route(ptr->model->re, route);
+    return rc != FWGPU_OK ? rc : fwgpu_debug_last_launch(ptr->model->re, launch, n);
 }
 
 int fwgpu_predictor_last_text_route(const FfiPredictor *ptr, uint64_t *lines, uint64_t *host_lines, int *fell_back) {

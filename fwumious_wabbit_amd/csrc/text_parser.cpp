@@ -518,6 +518,57 @@ int text_lines_place(fwgpu_text_parser *tp, uint32_t *d_records) {
     return FWGPU_OK;
 }
 
+// ---- many requests' lines in ONE plain pass whose results stay on the device (serving.cpp fwgpu_predictor_predict_requests_text): line index, status
+// pass, the records' offsets by the plan's scan (one window, no host lines), write pass.  Nothing but the line count comes to the host; everything else
+// is enqueued on the parser's stream when the call returns.  The text ends in a newline and fits one pass.
+uint64_t text_device_max_bytes() { return kChunkBytes; }
+uint32_t text_parser_namespaces(const fwgpu_text_parser *tp) { return tp->ns.num_namespaces; }
+
+int text_lines_device(fwgpu_text_parser *tp, const char *text, uint32_t len, TextDeviceLines *out) {
+    if (!tp || !text || !out || len == 0 || len > kChunkBytes || text[len - 1] != '\n') return fail(FWGPU_ERR_INVALID, "text_lines_device: bad argument");
+    FWGPU_HIP(hipSetDevice(tp->device));
+    tp->last_lines = tp->last_host_lines = 0;
+    tp->mode = LineMode();
+    tp->mode.set_word1 = 1;  // serving: every record's label word is 0
+    if (tp->chunks.empty()) tp->chunks.emplace_back(new TextChunk());
+    TextChunk &ch = *tp->chunks[0];
+    int rc = upload_text(tp, ch, text, len);
+    if (!rc) rc = chunk_status(tp, ch, /*tail=*/false, /*fetch=*/false);
+    if (rc) return rc;
+    const uint32_t n = ch.nlines;
+    tp->last_lines = n;
+    const size_t tmp = text_plan_temp_bytes(n);
+    if ((rc = tp->plan_tmp.ensure(tmp))) return rc;
+    if ((rc = tp->plan_out.ensure(8 * (size_t)kTextPlanStats))) return rc;
+    if ((rc = tp->train[0].rec_off.ensure(8 * ((size_t)n + 1)))) return rc;
+    // a record has at most header + slots + one word per byte of its line
+    if ((rc = tp->words.ensure(4 * ((size_t)len + (size_t)n * (tp->ns.num_namespaces + 4) + 16)))) return rc;
+    uint64_t *d_off = tp->train[0].rec_off.as<uint64_t>();
+    FWGPU_HIP(text_batch_plan(ch.status.as<uint4>(), n, std::max<uint32_t>(n, 1), kTextNoHoldout, d_off, tp->plan_out.as<uint64_t>(), nullptr, 0, nullptr,
+                              tp->plan_tmp.p, tp->plan_tmp.cap, tp->stream));
+    TextParseArgs a{};
+    a.text = ch.text.as<unsigned char>();
+    a.lstart = ch.lstart.as<uint32_t>();
+    a.nlines = n;
+    a.ns = tp->ns;
+    a.set_word1 = 1;
+    a.status = ch.status.as<uint4>();
+    a.n_used = n;
+    a.dst_off = d_off;
+    a.dst = tp->words.as<uint32_t>();
+    a.long_list = ch.long_list.as<uint32_t>();
+    a.long_count = tp->long_count;
+    FWGPU_HIP(text_parse_launch(a, true, tp->stream));
+    out->text = a.text;
+    out->lstart = a.lstart;
+    out->status = a.status;
+    out->records = a.dst;
+    out->rec_off = d_off;
+    out->nlines = n;
+    out->stream = tp->stream;
+    return FWGPU_OK;
+}
+
 // ---- training from text (trainer.cpp fwgpu_trainer_digest_text_device): a piece of text -> records, offsets and launch statistics in one of the
 // parser's two sets of device buffers.  Status pass, then the host parses exactly the lines the kernel listed as NEEDS_HOST and writes their
 // {HOST_DONE, length, LR entries, FFM entries} into the status array, then text_batch_plan places every record and sums every launch window, then

@@ -28,6 +28,11 @@ def _lib():
         L.fwgpu_predictor_predict_requests.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_uint32),
                                                        C.POINTER(C.c_void_p)]
         L.fwgpu_predictor_predict_requests.restype = C.c_int
+        L.fwgpu_predictor_predict_requests_text.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64),
+                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.fwgpu_predictor_predict_requests_text.restype = C.c_int
+        L.fwgpu_predictor_last_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_uint32]
+        L.fwgpu_predictor_last_launch.restype = C.c_int
         L.fwgpu_predictor_apply_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.fwgpu_predictor_apply_diff.restype = C.c_int
         L._fw_ffi_ready = True
@@ -50,6 +55,27 @@ def predict_requests(predictors, requests):
     out_ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data if o.size else None for o in outs])
     capi.check(L.fwgpu_predictor_predict_requests(handles, n, inputs, counts, out_ptrs))
     return outs
+
+
+def predict_requests_text(predictors, texts, caps=None):
+    """predict_requests from the requests' TEXT (fwgpu_predictor_predict_requests_text): texts[r] is request r's candidates as bytes, one per line (a
+    last line may lack its newline), scanned, translated and filtered on the device.  Returns one float32 array per request, bit for bit what
+    predict_requests returns for the lines with their newlines; predictors[0].last_text_route() tells lines, host-parsed lines and whether the call
+    fell back to predict_requests.  caps[r]: lines request r's output holds (default: its newlines + 1)."""
+    if len(predictors) != len(texts):
+        raise ValueError("one text per predictor")
+    L = _lib()
+    n = len(predictors)
+    caps = [t.count(b"\n") + 1 for t in texts] if caps is None else list(caps)
+    outs = [np.zeros(max(c, 1), dtype=np.float32) for c in caps]
+    handles = (C.c_void_p * max(n, 1))(*[p.p for p in predictors])
+    ptrs = (C.c_char_p * max(n, 1))(*texts)
+    lens = (C.c_uint64 * max(n, 1))(*[len(t) for t in texts])
+    out_ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    c_caps = (C.c_uint64 * max(n, 1))(*caps)
+    n_lines = (C.c_uint64 * max(n, 1))()
+    capi.check(L.fwgpu_predictor_predict_requests_text(handles, n, ptrs, lens, out_ptrs, c_caps, n_lines))
+    return [o[: n_lines[r]] for r, o in enumerate(outs)]
 
 
 class Predictor:
@@ -97,6 +123,12 @@ class Predictor:
         n, h, f = C.c_uint64(), C.c_uint64(), C.c_int()
         capi.check(self.L.fwgpu_predictor_last_text_route(self.p, C.byref(n), C.byref(h), C.byref(f)))
         return n.value, h.value, bool(f.value)
+
+    def last_launch(self):
+        """(capi.ROUTE_* of the last batch launch of this predictor's model, the dict Regressor.last_launch gives for it) -- fwgpu_predictor_last_launch"""
+        route, out = C.c_int(-1), (C.c_int32 * len(capi.LAUNCH_INFO))()
+        capi.check(self.L.fwgpu_predictor_last_launch(self.p, C.byref(route), out, len(capi.LAUNCH_INFO)))
+        return route.value, dict(zip(capi.LAUNCH_INFO, (int(x) for x in out)))
 
     def apply_diff(self, diff: bytes):
         """patches a --packed_weights model in place from the byte-diff stream of the file it was loaded from and the next published file

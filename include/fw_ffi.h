@@ -74,6 +74,22 @@ int fwgpu_predictor_last_text_route(const FfiPredictor *p, uint64_t *lines, uint
 int fwgpu_predictor_predict_requests(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *const *inputs,
                                      const uint32_t *n_inputs, float *const *out);
 
+/* The same launch from the requests' TEXT: texts[r] (lens[r] bytes) holds request r's candidates, one per line (a last line may lack its
+ * newline); out[r][j] is bit for bit what fwgpu_predictor_predict_requests returns for line j of request r given with its newline,
+ * n_lines[r] the number of lines of request r; FWGPU_ERR_RANGE when a caps[r] is smaller.  The device parser scans all texts in one
+ * pass, and the device decides every line's cache rule against its own request's cache, translates it on top of that request's
+ * context and writes the filtered entries into the entry batch: no host parser, translator or filter.  A call in which some line is
+ * not the device parser's, does not start with '|', names a namespace of its context again or repeats a cached feature goes through
+ * fwgpu_predictor_predict_requests on the split lines, whole, with the same numbers (fwgpu_predictor_last_text_route on
+ * predictors[0]: fell_back), as do FWGPU_SERVING_HOST_PARSE=1 and more than 16 MiB of text.  Refusals: those of
+ * fwgpu_predictor_predict_requests, with its messages. */
+int fwgpu_predictor_predict_requests_text(FfiPredictor *const *predictors, uint32_t n_requests, const char *const *texts, const uint64_t *lens,
+                                          float *const *out, const uint64_t *caps, uint64_t *n_lines);
+
+/* Which path (FWGPU_ROUTE_*) and kernel (fwgpu_debug_last_launch's words, the first n of them) the model's regressor took in its last batch
+ * launch: what fwgpu_debug_last_route / fwgpu_debug_last_launch say of a regressor, for the one a predictor and its clone_lite copies share. */
+int fwgpu_predictor_last_launch(const FfiPredictor *p, int *route, int32_t *launch, uint32_t n);
+
 /* Not in the reference's FFI (its weight_patcher rewrites the file): patches a --packed_weights model in place from the bare byte-diff stream
  * of the file it was loaded from and the next published file (include/fwgpu.h: fwgpu_image_diff, fwgpu_diff_bytes; fwgpu_packed_apply_diff
  * states the refusals).  Runs under the model's mutex; the prototype and every clone_lite copy share the tables and see the patch.
