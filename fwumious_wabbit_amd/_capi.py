@@ -31,6 +31,7 @@ KERNEL_SCALAR, KERNEL_VEC4, KERNEL_RESIDENT, KERNEL_PACKED, KERNEL_REQUESTS, KER
 KERNEL_HEAD_FUSED = 7
 KERNEL_PACKED_HEAD = 8
 KERNEL_PACKED_HEAD_REQUESTS = 9
+HEAD_STEP_SUMMED, HEAD_STEP_PER_EXAMPLE = 0, 1  # fwgpu_head_set_step_rule
 LAUNCH_INFO = ("family", "chunks", "window", "chain", "no_kept_rows", "lds_keep", "threads", "lds_bytes")
 NN_INIT = {"xavier": 0, "hu": 1, "one": 2, "zero": 3}
 
@@ -269,6 +270,8 @@ def lib():
         "fwgpu_enable_fused_head": [vp],
         "fwgpu_fused_head_state": [vp, P(i32), P(u64), P(u64)],
         "fwgpu_debug_head_forward_time": [vp, u32, i32, u32, P(C.c_float), vp],
+        "fwgpu_head_set_step_rule": [vp, i32],
+        "fwgpu_head_get_step_rule": [vp, P(i32)],
         "fwgpu_debug_block_cache_read": [vp, vp, vp, vp, P(u64)],
         "fwgpu_debug_requests_time": [vp, vp, i32, u32, P(f32)],
         "fwgpu_quantize_ffm_table": [vp, vp, u64, P(u64)],

@@ -660,6 +660,8 @@ struct fwgpu_regressor {
     float *d_nn_w = nullptr, *d_nn_acc = nullptr, *d_lut_nn = nullptr;
     uint64_t nn_len = 0;
     void *head_scratch = nullptr;  // mini-batched head (head.hip): activations, masks, gradients of the current batch
+    int32_t head_step_rule = FWGPU_HEAD_STEP_SUMMED;  // fwgpu_head_set_step_rule: how head_step's training steps move the dense weights
+    int32_t head_seq_tj = 0;                          // debug option 16: tile rows of the per-example rule's kernel (0: kHeadSeqTJ)
     float *pred_x = nullptr, *pred_yi = nullptr;  // predict-only batches of a model with a deep head: x [n * X] and {label, importance} [2n] of the batch in flight
     uint32_t pred_cap = 0;
     uint32_t pred_n = 0;                   // examples whose x the last batched predict launch left in pred_x (0: the last batch launch took another route)
@@ -921,6 +923,26 @@ int split_update(fwgpu_regressor *r, fwgpu_batch *b, fwgpu_split *sp, int mode, 
 // mini-batched deep head on the records' x (head.hip): forward, sigmoid, backward, one AdaGrad step per dense weight
 int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, float *d_pred, bool update, hipStream_t stream);
 void head_scratch_free(fwgpu_regressor *r);
+// the per-example step rule of that head (head_seq.hip; fwgpu_head_set_step_rule): every dense weight takes the batch's per-example steps in example order,
+// from registers.  A segment is one layer's weights with its operands: G_e(j, i) = dz[e * ld_dz + j] * in[e, i], where columns [0, w0) of `in` come from
+// src0 [n, w0], [w0, w0 + w1) from src1 [n, w1] (the final neuron's [h_last | x]) and column w0 + w1 is the bias (input 1).
+struct HeadSeqSeg {
+    const float *dz, *src0, *src1;
+    uint32_t ld_dz, w0, w1, rows;
+    uint32_t off;             // float offset of the layer in w / acc: W[j * in + i], then the biases
+    uint32_t tile0, tiles_i;  // the segment's first workgroup; tiles along i
+    uint32_t vec;             // the input rows may be loaded 16 bytes at a time (row lengths % 4 == 0, 16-byte aligned bases)
+};
+struct HeadSeqPlan {
+    HeadSeqSeg seg[kNnMaxLayers + 1];
+    uint32_t n_seg, n_tiles, n;
+    float *w, *acc;
+    const float *lut;
+    float rate, minus_power_t;
+};
+constexpr int kHeadSeqTJ = 16;  // rows of a workgroup's tile: 16 or 32 (profiles/head_step_rule.json; fwgpu_debug_set_option 16 for A/B runs)
+HeadSeqPlan head_seq_plan(const DevNN &nn, const float *x, float *const *h, float *const *dz, const float *gvec, uint32_t n, int tj);
+hipError_t launch_head_seq(const HeadSeqPlan &p, int optimizer, int tj, hipStream_t s);
 // the predict-only forward of the whole head in one launch, a workgroup per 32 examples (head_fused.hip).  head_fused_lds_bytes: the workgroup's LDS, 0 where the
 // kernel does not serve the regressor's head (it does not fit the CU's LDS: the caller keeps head_step)
 size_t head_fused_lds_bytes(const fwgpu_regressor *r);

@@ -7,6 +7,7 @@
 // "split pipeline") the dense weights are frozen, the batch goes through the layers as GEMMs on
 // v_mfma_f32_32x32x2_f32 (exact f32, 157 TFLOP/s peak), the weight gradients are SUMMED over the batch and every dense weight
 // takes ONE optimizer step with the sum.  oracle/fw_oracle.c fwo_learn_minibatch is the CPU statement of the same mode.
+// (fwgpu_head_set_step_rule selects the other rule: one step per weight and EXAMPLE from the same frozen-weight gradients -- head_seq.hip.)
 //
 //   x [n, X]  --W1-->  z1 -relu-> h1 [n, w1]  --W2-->  z2 -relu-> h2 [n, w2] ...   logit = w_f . [h_last | x] + b_f   (topology one)
 //   g = -(y - p) * importance ;  d h_last = g * w_f[:wl] ;  dx = g * w_f[wl:]  (+ the path through the layers)
@@ -416,9 +417,12 @@ int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, f
                        hs.dz[L - 1], dx, (int)n, (int)wl, (int)X, nn.topology == 1 ? 1 : 0, update ? 1 : 0, rows);
     FWGPU_HIP(hipGetLastError());
     if (!update) return FWGPU_OK;
+    // fwgpu_head_set_step_rule: under the per-example rule no gradient sum is formed -- the input-gradient products run as ever, then head_seq.hip steps
+    // every dense weight once per example from dz, the layers' inputs and gvec, after every product that reads W
+    const bool per_example = r->head_step_rule == FWGPU_HEAD_STEP_PER_EXAMPLE;
     float *dW = hs.dw;
     // final neuron's weight gradients: sum_e g_e * [h_last | x]_e, bias: sum_e g_e
-    {
+    if (!per_example) {
         float *dwf = dW + nn.off[L];
         hipLaunchKernelGGL(head_colsum_kernel, dim3((wl + 63) / 64), dim3(64 * kColsumGroups), 0, stream, hs.h[L - 1], hs.gvec, dwf, (int)n, (int)wl, (int)wl);
         if (nn.topology == 1)
@@ -431,16 +435,22 @@ int head_step(fwgpu_regressor *r, fwgpu_split *sp, uint32_t first, uint32_t n, f
         const float *W = nn.w + nn.off[l];
         const uint32_t out = nn.out[l], inw = nn.in[l];
         const float *lin = l == 0 ? x : hs.h[l - 1];
-        // dW_l[j, i] = sum_e dz[e, j] * in[e, i]
-        FWGPU_HIP((gemm<true, false, 0>(hs.dz[l], lin, dW + nn.off[l], (int)out, (int)inw, (int)n, (int)out, (int)inw, (int)inw, nullptr, nullptr, 0, stream)));
-        hipLaunchKernelGGL(head_colsum_kernel, dim3((out + 63) / 64), dim3(64 * kColsumGroups), 0, stream, hs.dz[l], (const float *)nullptr,
-                           dW + nn.off[l] + (size_t)inw * out, (int)n, (int)out, (int)out);
-        FWGPU_HIP(hipGetLastError());
+        if (!per_example) {  // dW_l[j, i] = sum_e dz[e, j] * in[e, i]
+            FWGPU_HIP((gemm<true, false, 0>(hs.dz[l], lin, dW + nn.off[l], (int)out, (int)inw, (int)n, (int)out, (int)inw, (int)inw, nullptr, nullptr, 0, stream)));
+            hipLaunchKernelGGL(head_colsum_kernel, dim3((out + 63) / 64), dim3(64 * kColsumGroups), 0, stream, hs.dz[l], (const float *)nullptr,
+                               dW + nn.off[l] + (size_t)inw * out, (int)n, (int)out, (int)out);
+            FWGPU_HIP(hipGetLastError());
+        }
         if (l > 0) {  // d in = dz . W, then through the previous layer's ReLU mask
             FWGPU_HIP((gemm<false, false, 2>(hs.dz[l], W, hs.dz[l - 1], (int)n, (int)inw, (int)out, (int)out, (int)inw, (int)inw, nullptr, hs.m[l - 1], 0, stream)));
         } else {  // BlockCopy sums the two branches into dx (block_misc.rs:456-475)
             FWGPU_HIP((gemm<false, false, 3>(hs.dz[0], W, dx, (int)n, (int)X, (int)out, (int)out, (int)inw, (int)X, nullptr, nullptr, 0, stream)));
         }
+    }
+    if (per_example) {  // ---- one optimizer step per dense weight and example, in example order
+        const int tj = r->head_seq_tj ? r->head_seq_tj : kHeadSeqTJ;
+        FWGPU_HIP(launch_head_seq(head_seq_plan(nn, x, hs.h, hs.dz, hs.gvec, n, tj), r->cfg.optimizer, tj, stream));
+        return FWGPU_OK;
     }
     // ---- one optimizer step per dense weight
     hipLaunchKernelGGL(head_apply_kernel, dim3(512), dim3(256), 0, stream, nn.w, nn.acc, dW, (unsigned long long)r->nn_len, r->cfg.optimizer, nn.rate,
@@ -517,7 +527,7 @@ extern "C" int fwgpu_debug_head_step(fwgpu_regressor *r, const float *x, const f
     }
     if (update) {
         back(dx, view.d_dx, nx);
-        back(dW, hs.dw, r->nn_len);
+        if (r->head_step_rule != FWGPU_HEAD_STEP_PER_EXAMPLE) back(dW, hs.dw, r->nn_len);  // (the per-example rule forms no gradient sum: the caller's dW is left as it was)
     }
     return done(ok ? FWGPU_OK : fail(FWGPU_ERR_DEVICE, "debug_head_step: read-back failed"));
 }

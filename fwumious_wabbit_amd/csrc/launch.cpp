@@ -931,6 +931,22 @@ int fwgpu_fused_head_state(const fwgpu_regressor *r, int *enabled, uint64_t *lds
     return FWGPU_OK;
 }
 
+int fwgpu_head_set_step_rule(fwgpu_regressor *r, int rule) {
+    if (!r) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    if (r->packed()) return fail(FWGPU_ERR_INVALID, "head_set_step_rule: a packed regressor only predicts, its head takes no training step");
+    if (!r->nn.n_layers) return fail(FWGPU_ERR_INVALID, "head_set_step_rule: the regressor has no deep head");
+    if (rule != FWGPU_HEAD_STEP_SUMMED && rule != FWGPU_HEAD_STEP_PER_EXAMPLE)
+        return fail(FWGPU_ERR_INVALID, "head_set_step_rule: unknown rule " + std::to_string(rule) + " (FWGPU_HEAD_STEP_SUMMED or FWGPU_HEAD_STEP_PER_EXAMPLE)");
+    r->head_step_rule = rule;
+    return FWGPU_OK;
+}
+
+int fwgpu_head_get_step_rule(const fwgpu_regressor *r, int *rule) {
+    if (!r || !rule) return fail(FWGPU_ERR_INVALID, "NULL argument");
+    *rule = r->head_step_rule;
+    return FWGPU_OK;
+}
+
 int fwgpu_debug_head_inputs(fwgpu_regressor *r, float *out, uint64_t n_floats) {
     if (!r || !out) return fail(FWGPU_ERR_INVALID, "NULL argument");
     if ((r->last_route != FWGPU_ROUTE_HEAD_BATCHED && r->last_route != FWGPU_ROUTE_REQUESTS && r->last_route != FWGPU_ROUTE_PACKED_HEAD) || !r->pred_n || !r->pred_x)

@@ -470,6 +470,10 @@ int fwgpu_debug_set_option(fwgpu_regressor *r, int option, int value) {
         if (value < -1 || value > 3) return fail(FWGPU_ERR_INVALID, "LDS-kept rows option: 0 .. 3, or -1 (automatic)");
         r->launch.lds_keep = value;
         return FWGPU_OK;
+    case 16:  // rows of a workgroup's weight tile in the per-example head step (head_seq.hip): 16 or 32, -1 = the build's default
+        if (value != -1 && value != 16 && value != 32) return fail(FWGPU_ERR_INVALID, "per-example head step tile option: 16, 32 or -1");
+        r->head_seq_tj = value < 0 ? 0 : value;
+        return FWGPU_OK;
     case 7: r->launch.prefetch = value ? 1 : 0; return FWGPU_OK;  // next-record prefetch of the v2 kernel's updating launches
     case 2:  // whole-line FFM row updates: 0 off, 1 auto (tables larger than the Infinity Cache; default), 2 always, 3 chained path always with float-granular accesses
         if (value < 0 || value > 3) return fail(FWGPU_ERR_INVALID, "window option: 0, 1, 2 or 3");

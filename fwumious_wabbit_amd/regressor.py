@@ -527,6 +527,22 @@ class Regressor:
         out["ms"] = ms.value
         return out
 
+    def set_head_step_rule(self, rule):
+        """how a training step of the mini-batched head moves the dense weights: capi.HEAD_STEP_SUMMED (default: one optimizer step per weight with the
+        batch's summed gradient) or capi.HEAD_STEP_PER_EXAMPLE (one step per weight and example, in example order: csrc/head_seq.hip) --
+        fwgpu_head_set_step_rule"""
+        check(self.L.fwgpu_head_set_step_rule(self.h, int(rule)))
+
+    def head_step_rule(self):
+        """capi.HEAD_STEP_SUMMED or capi.HEAD_STEP_PER_EXAMPLE -- fwgpu_head_get_step_rule"""
+        rule = C.c_int32(-1)
+        check(self.L.fwgpu_head_get_step_rule(self.h, C.byref(rule)))
+        return rule.value
+
+    def set_head_step_tile(self, rows):
+        """rows of a workgroup's weight tile in the per-example head step: 16, 32 or -1 (the default) -- fwgpu_debug_set_option 16 (A/B runs)"""
+        check(self.L.fwgpu_debug_set_option(self.h, 16, int(rows)))
+
     def set_prefetch(self, on):
         """updating launches copy the next example's record to LDS during the current example (fwgpu_debug_set_option 7; default on)"""
         check(self.L.fwgpu_debug_set_option(self.h, 7, int(bool(on))))

@@ -572,6 +572,8 @@ int fwgpu_debug_set_kernel_version(fwgpu_regressor *r, int version);
  * option 14: predict-only HOGWILD batches of 256 or more examples of a model with a deep head: 1 (default, -1) = the batched route (the example kernel leaves every example's
  *   head input in a batch buffer, the layers run as GEMMs over slabs of examples: DESIGN.md 4.4) where the shape allows it; 0 = the per-example forward for every launch.
  *   -1 follows FWGPU_HEAD_PREDICT_PER_EXAMPLE (set: per example), a value set here overrides it.
+ * option 16: rows of a workgroup's weight tile in the per-example step of the mini-batched head (fwgpu_head_set_step_rule, csrc/head_seq.hip): 16 (default, -1) or 32
+ *   (A/B runs: profiles/head_step_rule.json).  The bits do not depend on it.
  * option 7: value 0 = the updating launches do not prefetch the next example's record (A/B runs; default 1).
  * option 8: rows per wave, beyond the 20 kept in registers, whose gather-time weights are parked in LDS for the update phase instead of
  *   being re-read (config-C-shaped rows on the chained path): 0..3, -1 (default) = as many as still let two workgroups share a CU.
@@ -933,6 +935,23 @@ int fwgpu_fused_head_state(const fwgpu_regressor *r, int *enabled, uint64_t *lds
  * head alone over the first n rows of x that the last batched head predict launch left on the device: fused != 0 the fused kernel (FWGPU_ERR_RANGE where
  * it does not serve the head), else the GEMM route (head_step, update = false).  pred (n floats, may be NULL): the last pass's predictions. */
 int fwgpu_debug_head_forward_time(fwgpu_regressor *r, uint32_t n, int fused, uint32_t reps, float *ms_per_pass, float *pred);
+/* ---- how a training step of the mini-batched head (fwgpu_learn_batch_sync on a model with a deep head; csrc/head.hip head_step) moves the dense weights.
+ * Forward, backward and the input gradients always run against the weights as the micro-batch found them.  Then
+ *   FWGPU_HEAD_STEP_SUMMED (default): the weight gradients are summed over the batch and every dense weight takes ONE optimizer step with the sum --
+ *     the oracle's fwo_learn_minibatch; under AdaGrad the accumulator grows by (sum g)^2;
+ *   FWGPU_HEAD_STEP_PER_EXAMPLE: every dense weight takes one optimizer step PER EXAMPLE, in example order, with that example's own gradient
+ *     G_e = fl(dz_l[e, j] * in_l[e, i]) (bias: dz_l[e, j]; final neuron: fl(g_e * [h_last | x][e, i]), bias g_e) -- the reference's learner
+ *     (block_neural.rs:252-340, optimizer.rs) up to a staleness of one micro-batch, and exactly it at a batch of one: the accumulator grows by
+ *     sum g^2, a batch of n makes n steps.  One launch of csrc/head_seq.hip: every weight and its accumulator sit in registers while the batch
+ *     streams past them through LDS; no gradient sum is formed, no atomics, two launches give the same bits.  An example that learns nothing
+ *     (general gradient 0) steps nothing.  The step itself is the summed rule's, statement for statement, for all three optimizers.
+ * The setter: FWGPU_ERR_INVALID on a regressor without a deep head, on a packed regressor (it only predicts) and on an unknown rule.  The rule may be
+ * set both ways at any time no step is in flight, and holds for every caller of head_step (fwgpu_learn_batch_sync, the host-walk of oversize examples,
+ * fwgpu_debug_head_step -- which under the per-example rule leaves the caller's dW buffer as it was).  Predict-only steps are the same under both. */
+#define FWGPU_HEAD_STEP_SUMMED 0       /* default: today's rule */
+#define FWGPU_HEAD_STEP_PER_EXAMPLE 1
+int fwgpu_head_set_step_rule(fwgpu_regressor *r, int rule);
+int fwgpu_head_get_step_rule(const fwgpu_regressor *r, int *rule);
 /* debug: a cache's contents as the device holds them -- T [F * F * k], dcf [F], cnt [F], the epoch it was set up at (each may be NULL).  Waits for the device. */
 int fwgpu_debug_block_cache_read(const fwgpu_block_cache *cache, float *T, float *dcf, uint32_t *cnt, uint64_t *epoch);
 /* debug (scripts/bench_serving_packed_requests.py): milliseconds per launch, by device events over `reps` launches on the null stream, of the
